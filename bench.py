@@ -5,9 +5,17 @@ One step = the hot path over one batch of synthetic audio already resident in HB
 GPU Kaldi Fbank (80 mel, mean-normalised) of 256 x 32000 samples -> ERes2NetV2 forward
 -> 256 x 192 embeddings.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--with-allgather]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--with-allgather] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the result line; nothing else.
+--dump-outputs DIR also writes the embeddings of the last timed step (what a caller of the
+timed path receives) as DIR/embeddings.npy, float32 [batch, 192] (DIR/embeddings_rank<r>.npy
+per rank when there is more than one); the inputs and weights are seeded, so two builds run
+with the same arguments can be compared output for output.  --full adds the legs that take
+runs of their own: the fp16x3 range-guard count (`exact_reruns`), the roofline objects and
+the CPU baseline; without it those keys of the result line are null.
 
 Multi-GPU: one process per GPU.  Under torch.distributed.run the ranks come from the
 environment; a bare `bench.py --gpus N` (N > 1, no WORLD_SIZE) spawns the N rank processes
@@ -18,7 +26,7 @@ max-over-ranks timing is the only communication, unless --with-allgather adds th
 exchange to every step (RCCL all-gather of the step's embeddings from every rank, then this
 rank's row block of the cosine affinity consumed by the top-k kernel,
 speakerlab/utils/distributed.py).  Rank 0 prints ONE JSON line, with the world size the
-process group reports.  The roofline object describes the dominant
+process group reports.  With --full the roofline object describes the dominant
 kernel (largest total time inside one forward), measured with HIP events on the stream
 the kernels run on; the CPU baseline is the oracle (op-for-op torch CPU restatement)
 timed on this host on a bounded sample.
@@ -54,7 +62,11 @@ def parse():
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--batch', type=int, default=BATCH)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the embeddings of the last timed step to DIR/embeddings.npy (float32)')
+    ap.add_argument('--full', action='store_true',
+                    help='also run the legs beyond the headline figure: range-guard count, rooflines, CPU baseline')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--cpu-passes', type=int, default=5, help='timed CPU-baseline passes (best is reported)')
     ap.add_argument('--with-allgather', action='store_true',
                     help='add the C4 exchange (all-gather of the step embeddings + row-block top-1) to every step')
@@ -370,8 +382,9 @@ def run(args):
     with torch.no_grad():
         for _ in range(args.warmup):
             step()
-            reruns += int(handle.last_forward_exact)   # untimed: checked after every warm-up forward
-            checked += 1
+            if args.full:
+                reruns += int(handle.last_forward_exact)   # untimed: checked after every warm-up forward
+                checked += 1
         torch.cuda.synchronize()
         if dist:
             tdist.barrier()
@@ -385,8 +398,13 @@ def run(args):
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         assert torch.isfinite(emb).all(), 'non-finite embeddings'
-        reruns += int(handle.last_forward_exact)       # the last timed forward (same input every step)
-        checked += 1
+        if args.full:
+            reruns += int(handle.last_forward_exact)   # the last timed forward (same input every step)
+            checked += 1
+        if args.dump_outputs:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            name = 'embeddings.npy' if world == 1 else f'embeddings_rank{rank}.npy'
+            np.save(os.path.join(args.dump_outputs, name), emb.float().cpu().numpy())
         if dist:
             t = torch.tensor([dt], device=device)
             tdist.all_reduce(t, op=tdist.ReduceOp.MAX)
@@ -404,16 +422,17 @@ def run(args):
             exchange = {'ms_per_step': round(e0.elapsed_time(e1) / reps, 4), 'rows_gathered': B * world,
                         'allgather_bytes': 4 * 192 * B * world,
                         'what': 'all_gather_embeddings (RCCL) + topk_row_block (spk_cosine_topk, k=1), rank 0'}
-        feats = _hip.fbank(wavs, 80, mean_nor=True)
-        roof = roofline(model, feats, device, args.traffic_json) if rank == 0 else None
-        if roof is not None:
+        roof = None
+        if args.full and rank == 0:
+            feats = _hip.fbank(wavs, 80, mean_nor=True)
+            roof = roofline(model, feats, device, args.traffic_json)
             roof['fbank'] = fbank_roofline(wavs, device)
 
     total_utts = B * args.steps * world
     value = total_utts / dt
     if rank == 0:
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             cpu = cpu_baseline(args.cpu_passes)
         flops = model._hip_handle(device).flops(198)
         line = {
@@ -441,7 +460,7 @@ def run(args):
             'model_gflop_per_utt': round(flops / 1e9, 3),
             'exchange': exchange,
             # the range guard's exact-fp32 re-run must never fire on this input
-            'exact_reruns': {'count': reruns, 'forwards_checked': checked},
+            'exact_reruns': {'count': reruns, 'forwards_checked': checked} if args.full else None,
             'roofline': roof,
             'cpu_baseline': cpu,
         }
