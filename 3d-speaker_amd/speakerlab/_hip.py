@@ -60,6 +60,12 @@ SYMBOLS = {
     'spk_fbank_f32': (ctypes.c_int, [_P, _P, ctypes.c_int32, _P, _P, ctypes.c_int32, ctypes.c_int32, _P]),
     'spk_fbank_f32_padded': (ctypes.c_int, [_P, _P, ctypes.c_int32, _P, _P, ctypes.c_int32, ctypes.c_int32,
                                             ctypes.c_int32, _P]),
+    'spk_resample_out_len': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                            ctypes.POINTER(ctypes.c_int64)]),
+    'spk_resample_taps': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
+                                         ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), _P,
+                                         ctypes.c_size_t]),
+    'spk_resample_f32': (ctypes.c_int, [_P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P]),
     'spk_model_create': (ctypes.c_int, [ctypes.POINTER(spk_model_config_t), ctypes.POINTER(spk_weight_t),
                                         ctypes.c_int32, ctypes.POINTER(_P)]),
     'spk_model_destroy': (ctypes.c_int, [_P]),
@@ -101,8 +107,11 @@ _lib = None
 _lock = threading.Lock()
 
 
+E_UNSUPPORTED = -6   # SPK_E_UNSUPPORTED
+
+
 class HipError(RuntimeError):
-    pass
+    code = None   # the SPK_E_* code when the library returned one
 
 
 def lib():
@@ -127,7 +136,9 @@ def lib():
 def _check(rc: int, what: str):
     if rc != 0:
         msg = lib().spk_last_error()
-        raise HipError(f'{what} failed ({rc}): {msg.decode() if msg else ""}')
+        err = HipError(f'{what} failed ({rc}): {msg.decode() if msg else ""}')
+        err.code = rc
+        raise err
 
 
 def _stream(device: torch.device) -> int:
@@ -206,6 +217,71 @@ def fbank_padded(wavs: torch.Tensor, lengths, n_mels: int = 80, mean_nor: bool =
                                           offs[1].data_ptr(), tmax, n_mels, int(bool(mean_nor)), _stream(dev)),
                'spk_fbank_f32_padded')
     return feats, torch.tensor(frames, dtype=torch.int32).to(dev, non_blocking=True)
+
+
+# ----------------------------------------------------------------------------- resampling
+def resample_out_len(n_samples: int, orig_freq: int, new_freq: int) -> int:
+    """Length of ``n_samples`` at ``orig_freq`` after resampling to ``new_freq``:
+    ceil(new * n / orig) in gcd-reduced rates (no GPU needed)."""
+    n = ctypes.c_int64()
+    _check(lib().spk_resample_out_len(int(n_samples), int(orig_freq), int(new_freq), ctypes.byref(n)),
+           'spk_resample_out_len')
+    return n.value
+
+
+def resample(wavs, orig_freq: int, new_freq: int, lengths=None):
+    """torchaudio.functional.resample(wavs, orig_freq, new_freq) (default arguments) on the GPU.
+
+    ``wavs``: a [B, L] or [L] float32 device tensor -> [B, L'] / [L']; with ``lengths`` (valid
+    samples per row) or as a list of 1-D device tensors the batch is ragged and the result is a
+    list of 1-D views into one buffer, which has the layout ``fbank(..., lengths=...)`` reads.
+    Every row's result has the bits it has when resampled alone.  Raises HipError (``.code``
+    the SPK_E_* value) for equal or non-positive rates and for a rate pair whose polyphase
+    table is above the library's cap (E_UNSUPPORTED)."""
+    as_list = isinstance(wavs, (list, tuple))
+    if as_list and lengths is not None:
+        raise HipError('resample: lengths goes with a [B, L] tensor, not with a list')
+    squeeze = False
+    if not as_list:
+        require_device_tensor(wavs, 'resample')
+        squeeze = wavs.dim() == 1
+        if squeeze:
+            wavs = wavs.unsqueeze(0)
+        if wavs.dim() != 2:
+            raise HipError(f'resample: expected [B, L] or [L], got {tuple(wavs.shape)}')
+        if lengths is not None:
+            lens = [int(v) for v in lengths]
+            if len(lens) != wavs.shape[0] or (lens and (min(lens) < 0 or max(lens) > wavs.shape[1])):
+                raise HipError('resample: need B lengths in [0, L]')
+            wavs, as_list = [wavs[i, :n] for i, n in enumerate(lens)], True
+    if as_list:
+        if len(wavs) == 0:
+            return []
+        for w in wavs:
+            require_device_tensor(w, 'resample')
+            if w.dim() != 1:
+                raise HipError('resample: a ragged batch is a list of 1-D tensors')
+        dev = wavs[0].device
+        lens = [int(w.numel()) for w in wavs]
+        flat = torch.cat([w.to(torch.float32) for w in wavs])
+    else:
+        dev = wavs.device
+        lens = [int(wavs.shape[1])] * int(wavs.shape[0])
+        flat = wavs.to(torch.float32).contiguous().view(-1)
+    B = len(lens)
+    in_off, out_off = [0], [0]
+    for n in lens:
+        in_off.append(in_off[-1] + n)
+        out_off.append(out_off[-1] + resample_out_len(n, orig_freq, new_freq))
+    offs = torch.tensor([in_off, out_off], dtype=torch.int64).to(dev, non_blocking=True)
+    out = torch.empty(out_off[-1], dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _check(lib().spk_resample_f32(flat.data_ptr(), offs[0].data_ptr(), B, int(orig_freq), int(new_freq),
+                                      out.data_ptr(), offs[1].data_ptr(), _stream(dev)), 'spk_resample_f32')
+    if as_list:
+        return [out[out_off[i]:out_off[i + 1]] for i in range(B)]
+    out = out.view(B, -1) if B else out.view(0, 0)
+    return out[0] if squeeze else out
 
 
 # ----------------------------------------------------------------------------- models

@@ -67,6 +67,9 @@ parser.add_argument('--model_cache_dir', default='pretrained', type=str,
                     help='MI355X build: directory holding iic/speech_eres2netv2_sv_zh-cn_16k-common/<ckpt>')
 parser.add_argument('--synthetic_weights', action='store_true',
                     help='MI355X build: deterministic random weights instead of a checkpoint (no network)')
+parser.add_argument('--gpu_resample', action='store_true',
+                    help='MI355X build: resample non-16 kHz input on the GPU (HIP windowed-sinc kernel) '
+                         'instead of the host conv1d')
 parser.add_argument('--vad', choices=['auto', 'ten_vad', 'energy'], default='auto',
                     help='MI355X build: VAD engine (TenVad when importable, else the energy stand-in)')
 
@@ -169,7 +172,8 @@ class Diarization3Dspeaker:
                  model_cache_dir=None, no_chunk_after_vad=False, vad_min_speech_ms=None, vad_max_silence_ms=None,
                  vad_energy_threshold=None, vad_boundary_expansion_ms=None, vad_boundary_energy_percentile=None,
                  vad_threshold=0.5, cluster_mer_cos=0.3, cluster_fix_cos_thr=0.3, cluster_min_cluster_size=0,
-                 chunk_dur=1.5, chunk_step=0.75, batch_size=64, synthetic_weights=False, vad='auto', group=None):
+                 chunk_dur=1.5, chunk_step=0.75, batch_size=64, synthetic_weights=False, vad='auto', group=None,
+                 gpu_resample=False):
         if include_overlap and hf_access_token is None:
             raise ValueError('hf_access_token is required when include_overlap is True.')
         if include_overlap:
@@ -193,6 +197,9 @@ class Diarization3Dspeaker:
         # of the cosine affinity per rank gathered for the clustering (every rank clusters the
         # same matrix; rank 0 writes).  None: one process does everything (the reference).
         self.group = group
+        # audio at another rate than self.fs: resampled by the HIP kernel on self.device instead
+        # of the host conv1d (fileio.load_audio(device=...)); same [1, L] CPU tensor either way
+        self.resample_device = self.device if gpu_resample and self.device.type == 'cuda' else None
         self.output_field_labels = None
         self.last_vad_time = self.last_vad_time_raw = self.last_vad_time_processed = None
         self.last_vad_masked_audio = self.last_vad_refined_mask = self.last_vad_processed_mask = None
@@ -205,7 +212,7 @@ class Diarization3Dspeaker:
                                                else float(vad_boundary_energy_percentile))
 
     def __call__(self, wav, wav_fs=None, speaker_num=None):
-        wav_data = load_audio(wav, wav_fs, self.fs)
+        wav_data = load_audio(wav, wav_fs, self.fs, device=self.resample_device)
         flags, wav_vad = self.do_vad(wav_data)
         processed, refined, vad_time = self.postprocess_vad(flags, wav_vad)
         hop = int(self.vad_frame_size_ms * self.fs / 1000)
@@ -371,7 +378,7 @@ def write_side_files(diar, wav_path, out_file, wav_id, elapsed, plot=True):
     cosines from a second embedding pass over the output segments) — reference :934-1066."""
     from speakerlab.utils.fileio import write_wav
     d = os.path.dirname(out_file)
-    wav = load_audio(wav_path, None, diar.fs)
+    wav = load_audio(wav_path, None, diar.fs, device=getattr(diar, 'resample_device', None))
     if plot:
         _save_vad_png(wav, diar.fs, diar.last_vad_time_raw, diar.last_vad_time_processed, diar.last_vad_time,
                       os.path.join(d, f'{wav_id}.vad.png'))
@@ -419,7 +426,8 @@ def main_process(rank, nprocs, args, wav_list, port=None):
         args.no_chunk_after_vad, args.vad_min_speech_ms, args.vad_max_silence_ms, args.vad_energy_threshold,
         args.vad_boundary_expansion_ms, args.vad_boundary_energy_percentile, args.vad_threshold,
         args.cluster_mer_cos, args.cluster_fix_cos_thr, args.cluster_min_cluster_size, args.chunk_dur,
-        args.chunk_step, args.batch_size, synthetic_weights=args.synthetic_weights, vad=args.vad, group=group)
+        args.chunk_step, args.batch_size, synthetic_weights=args.synthetic_weights, vad=args.vad, group=group,
+        gpu_resample=args.gpu_resample)
     # one file per process, as the reference (:924); with --shard_chunks every rank takes part
     # in every file and rank 0 writes the outputs
     mine = wav_list if group is not None else wav_list[rank::nprocs]

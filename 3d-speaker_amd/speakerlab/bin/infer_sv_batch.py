@@ -21,7 +21,8 @@ NameError on ``wav_file`` (``infer_sv_batch.py:404-405``), the bare ``except`` a
 catches it, prints the read warning and skips the file -- no embedding is written.
 ``--resample_non16k`` (MI355X-build opt-in, off by default) instead resamples such files
 with ``speakerlab.utils.fileio.resample`` (torchaudio's windowed-sinc resampler; the
-reference's intended sox ``rate`` effect is not available here).
+reference's intended sox ``rate`` effect is not available here); ``--resample_device gpu``
+moves that resampling from the I/O threads to the HIP kernel behind ``_hip.resample``.
 """
 import argparse
 import os
@@ -53,6 +54,9 @@ parser.add_argument('--nprocs', default=None, type=int, help='MI355X build: numb
 parser.add_argument('--io_threads', default=8, type=int, help='MI355X build: wav reader threads per process')
 parser.add_argument('--resample_non16k', action='store_true',
                     help='MI355X build: resample non-16 kHz wavs (the reference skips them, see module doc)')
+parser.add_argument('--resample_device', choices=['host', 'gpu'], default='host',
+                    help='MI355X build, with --resample_non16k: host = torch conv1d in the I/O threads; '
+                         'gpu = the HIP windowed-sinc kernel, one ragged call per source rate and batch')
 
 
 def _spec(obj, **args):
@@ -115,6 +119,12 @@ class SampleRateSkip(Exception):
     """A non-16 kHz wav: the reference's load_wav fails on it (NameError, :404-405)."""
 
 
+def wav_to_chunks(wav, obj_fs=SAMPLE_RATE, chunk_size=CHUNK_SECONDS, max_load_len=MAX_LOAD_SECONDS):
+    """Mono wav at ``obj_fs`` -> its first ``max_load_len`` seconds as [n_chunks, chunk] (host or device)."""
+    wav = wav[:int(max_load_len * obj_fs)]
+    return chunk_wav(wav, int(chunk_size * obj_fs))
+
+
 def load_wav_chunks(path, obj_fs=SAMPLE_RATE, chunk_size=CHUNK_SECONDS, max_load_len=MAX_LOAD_SECONDS,
                     resample_other_rates=False):
     from speakerlab.utils.fileio import read_wav, resample
@@ -124,8 +134,53 @@ def load_wav_chunks(path, obj_fs=SAMPLE_RATE, chunk_size=CHUNK_SECONDS, max_load
             raise SampleRateSkip(f'sample rate {fs} != {obj_fs}; the reference skips such files')
         wav = resample(wav, fs, obj_fs)
     wav = wav.mean(dim=0)
-    wav = wav[:int(max_load_len * obj_fs)]
-    return chunk_wav(wav, int(chunk_size * obj_fs))
+    return wav_to_chunks(wav, obj_fs, chunk_size, max_load_len)
+
+
+class NativeRateWav:
+    """What an I/O thread hands over for ``--resample_device gpu``: the mono waveform at the
+    file's own rate; the main thread resamples a batch of them in one call per rate."""
+
+    def __init__(self, wav, fs, obj_fs=SAMPLE_RATE, chunk_size=CHUNK_SECONDS, max_load_len=MAX_LOAD_SECONDS):
+        # the first max_load_len seconds of the output need that much input and the filter's
+        # reach (6 / (0.99 min(fs, obj_fs)) s): a second more than covers it
+        self.wav, self.fs = wav[:int((max_load_len + 1) * fs)], int(fs)
+        n_out = min(int(np.ceil(self.wav.shape[0] * obj_fs / fs)), int(max_load_len * obj_fs))
+        self.n_chunks = int(np.ceil(n_out / int(chunk_size * obj_fs)))
+
+
+def load_wav_native(path, obj_fs=SAMPLE_RATE, chunk_size=CHUNK_SECONDS, max_load_len=MAX_LOAD_SECONDS):
+    """16 kHz files: their chunks, as load_wav_chunks; other rates: a NativeRateWav."""
+    from speakerlab.utils.fileio import read_wav
+    wav, fs = read_wav(path)
+    wav = wav.mean(dim=0)
+    if fs == obj_fs:
+        return wav_to_chunks(wav, obj_fs, chunk_size, max_load_len)
+    return NativeRateWav(wav, fs, obj_fs, chunk_size, max_load_len)
+
+
+def gpu_resample_chunks(items, device, obj_fs=SAMPLE_RATE, chunk_size=CHUNK_SECONDS, max_load_len=MAX_LOAD_SECONDS):
+    """NativeRateWavs -> their device chunk tensors (in order): the files of one source rate
+    are resampled as one ragged batch by the HIP kernel (_hip.resample), then cut by the host
+    path's own truncation / chunk_wav code."""
+    from speakerlab import _hip
+    out = [None] * len(items)
+    for fs in sorted({it.fs for it in items}):
+        idx = [i for i, it in enumerate(items) if it.fs == fs]
+        lens = [items[i].wav.shape[0] for i in idx]
+        flat = torch.cat([items[i].wav for i in idx]).pin_memory().to(device, non_blocking=True)
+        pos = np.cumsum([0] + lens)
+        try:
+            res = _hip.resample([flat[pos[k]:pos[k + 1]] for k in range(len(idx))], fs, obj_fs)
+        except _hip.HipError as e:
+            if e.code != _hip.E_UNSUPPORTED:
+                raise
+            # a rate pair above the kernel's table cap: the host resampler
+            from speakerlab.utils.fileio import resample
+            res = [resample(items[i].wav, fs, obj_fs).to(device) for i in idx]
+        for i, r in zip(idx, res):
+            out[i] = wav_to_chunks(r, obj_fs, chunk_size, max_load_len)
+    return out
 
 
 def build_model(conf, args, local_dir):
@@ -143,15 +198,21 @@ def wav_id_of(path):
     return os.path.basename(path).rsplit('.', 1)[0]
 
 
-def extract(model, wav_paths, batch_size, device, on_result, io_threads=8, progress=None, resample_other_rates=False):
+def extract(model, wav_paths, batch_size, device, on_result, io_threads=8, progress=None, resample_other_rates=False,
+            resample_device='host'):
     """Stream wavs -> chunks -> GPU Fbank + forward -> per-wav mean embedding.
 
-    ``on_result(wav_id, embedding[np.float32, E])`` is called in input order."""
+    ``on_result(wav_id, embedding[np.float32, E])`` is called in input order.
+    ``resample_device='gpu'`` (with ``resample_other_rates``): the I/O threads only read and
+    average the channels of non-16 kHz files; the batch's files are resampled on the device."""
+    gpu_rs = resample_other_rates and resample_device == 'gpu'
     from speakerlab.process.processor import FBank
     fbank = FBank(80, sample_rate=SAMPLE_RATE, mean_nor=True)
 
     def safe_load(p):
         try:
+            if gpu_rs:
+                return load_wav_native(p)
             return load_wav_chunks(p, resample_other_rates=resample_other_rates)
         except Exception as e:   # reference: warn and skip unreadable files (:361-365)
             print(f'[WARNING]: Error reading {p}, please check. ({e})')
@@ -163,8 +224,16 @@ def extract(model, wav_paths, batch_size, device, on_result, io_threads=8, progr
         nonlocal buf_ids, buf_chunks, n_buf
         if not buf_ids:
             return
-        pos = np.cumsum([0] + [c.shape[0] for c in buf_chunks])
-        wavs = torch.cat(buf_chunks).pin_memory().to(device, non_blocking=True)
+        pos = np.cumsum([0] + [c.n_chunks if isinstance(c, NativeRateWav) else c.shape[0] for c in buf_chunks])
+        host = [c for c in buf_chunks if not isinstance(c, NativeRateWav)]
+        if len(host) == len(buf_chunks):
+            wavs = torch.cat(buf_chunks).pin_memory().to(device, non_blocking=True)
+        else:
+            native = gpu_resample_chunks([c for c in buf_chunks if isinstance(c, NativeRateWav)], device)
+            if host:
+                up = torch.cat(host).pin_memory().to(device, non_blocking=True)
+                host = list(torch.split(up, [c.shape[0] for c in host]))
+            wavs = torch.cat([native.pop(0) if isinstance(c, NativeRateWav) else host.pop(0) for c in buf_chunks])
         with torch.no_grad():
             emb = model(fbank.batch(wavs)).cpu().numpy()
         for i, wid in enumerate(buf_ids):
@@ -179,7 +248,7 @@ def extract(model, wav_paths, batch_size, device, on_result, io_threads=8, progr
                 continue
             buf_ids.append(wav_id_of(path))
             buf_chunks.append(chunks)
-            n_buf += chunks.shape[0]
+            n_buf += chunks.n_chunks if isinstance(chunks, NativeRateWav) else chunks.shape[0]
             if n_buf >= batch_size:
                 flush()
         flush()
@@ -213,7 +282,7 @@ def main_process(rank, nprocs, args, wav_list, conf, local_dir):
         from tqdm import tqdm
         pbar = tqdm(total=e - s, desc='Processing')
     extract(model, wav_list[s:e], args.batch_size, device, on_result, args.io_threads, pbar,
-            getattr(args, 'resample_non16k', False))
+            getattr(args, 'resample_non16k', False), getattr(args, 'resample_device', 'host'))
     if pbar is not None:
         pbar.close()
     if writer is not None:

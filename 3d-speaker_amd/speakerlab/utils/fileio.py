@@ -58,14 +58,41 @@ def sinc_resample_kernel(orig_freq: int, new_freq: int, gcd: int, lowpass_filter
     return kernels, width
 
 
+def _is_gpu(device) -> bool:
+    return device is not None and torch.device(device).type == 'cuda'
+
+
+def _resample_gpu(waveform: torch.Tensor, orig_freq: int, new_freq: int, device) -> torch.Tensor:
+    """``resample`` through the HIP kernel (_hip.resample): upload, resample, and hand the result
+    back where and as the host path would (same device, dtype and leading shape)."""
+    from speakerlab import _hip
+    shape = waveform.size()
+    x = waveform.reshape(-1, shape[-1]).to(torch.device(device), torch.float32)
+    y = _hip.resample(x, int(orig_freq), int(new_freq))
+    return y.reshape(shape[:-1] + (y.shape[-1],)).to(waveform.device, waveform.dtype)
+
+
 def resample(waveform: torch.Tensor, orig_freq: int, new_freq: int, lowpass_filter_width: int = 6,
-             rolloff: float = 0.99) -> torch.Tensor:
+             rolloff: float = 0.99, device=None) -> torch.Tensor:
     """torchaudio.functional.resample(waveform, orig_freq, new_freq) with its defaults: any
-    leading shape, time last; output length ceil(new * L / orig) in gcd-reduced rates."""
+    leading shape, time last; output length ceil(new * L / orig) in gcd-reduced rates.
+
+    ``device`` (opt-in, a ROCm device): the convolution runs there on the HIP resampler (taps
+    built in double, so closer to the exact formula than this fp32 host path); the result comes
+    back with the waveform's placement, dtype and shape.  The kernel implements the default
+    filter only, and refuses rate pairs whose polyphase table is above its cap: both cases
+    take the host path."""
     if orig_freq <= 0 or new_freq <= 0:
         raise ValueError('Original frequency and desired frequecy should be positive')
     if orig_freq == new_freq:
         return waveform
+    if _is_gpu(device) and lowpass_filter_width == 6 and rolloff == 0.99 and waveform.is_floating_point():
+        from speakerlab import _hip
+        try:
+            return _resample_gpu(waveform, orig_freq, new_freq, device)
+        except _hip.HipError as e:
+            if e.code != _hip.E_UNSUPPORTED:
+                raise
     g = math.gcd(int(orig_freq), int(new_freq))
     kernel, width = sinc_resample_kernel(orig_freq, new_freq, g, lowpass_filter_width, rolloff,
                                          waveform.dtype, waveform.device)
@@ -80,16 +107,18 @@ def resample(waveform: torch.Tensor, orig_freq: int, new_freq: int, lowpass_filt
     return y[..., :target].reshape(shape[:-1] + (min(target, y.shape[-1]),))
 
 
-def _resample(wav: torch.Tensor, fs: int, obj_fs: int) -> torch.Tensor:
-    return resample(wav, fs, obj_fs)
+def _resample(wav: torch.Tensor, fs: int, obj_fs: int, device=None) -> torch.Tensor:
+    return resample(wav, fs, obj_fs, device=device)
 
 
-def load_audio(input, ori_fs=None, obj_fs=None):
+def load_audio(input, ori_fs=None, obj_fs=None, device=None):
+    """``device`` (opt-in, a ROCm device): audio at another rate than ``obj_fs`` is resampled
+    there (``resample``); the result is the CPU [1, L'] tensor of the host path either way."""
     if isinstance(input, str):
         wav, fs = read_wav(input)
         wav = wav.mean(dim=0, keepdim=True)
         if obj_fs is not None and fs != obj_fs:
-            wav = _resample(wav, fs, obj_fs)
+            wav = _resample(wav, fs, obj_fs, device)
         return wav
     if isinstance(input, (np.ndarray, torch.Tensor)):
         wav = torch.from_numpy(input) if isinstance(input, np.ndarray) else input
@@ -104,6 +133,6 @@ def load_audio(input, ori_fs=None, obj_fs=None):
         if wav.ndim == 1:
             wav = wav.unsqueeze(0)
         if ori_fs is not None and obj_fs is not None and ori_fs != obj_fs:
-            wav = _resample(wav, ori_fs, obj_fs)
+            wav = _resample(wav, ori_fs, obj_fs, device)
         return wav
     return input

@@ -16,6 +16,8 @@
  *   spk_fbank_f32        speakerlab/process/processor.py:133-158 (FBank.__call__ ->
  *                        torchaudio.compliance.kaldi.fbank) and the C++ runtime's
  *                        FbankComputer::compute_feature runtime/onnxruntime/feature/feature_fbank.cpp:22-91
+ *   spk_resample_f32     torchaudio.functional.resample as called by load_audio,
+ *                        speakerlab/utils/fileio.py:105-129
  *   spk_model_create     model construction + strict load_state_dict in
  *                        speakerlab/bin/infer_sv_batch.py:247-253 (and the ONNX session
  *                        runtime/onnxruntime/model/speaker_embedding_model.cpp:7-40)
@@ -110,6 +112,29 @@ int spk_fbank_f32(const float* wav, const int64_t* wav_offsets, int32_t n_utt, f
  * The input of spk_model_forward_lengths for variable-length batches. */
 int spk_fbank_f32_padded(const float* wav, const int64_t* wav_offsets, int32_t n_utt, float* feats,
                          const int64_t* frame_offsets, int32_t t_max, int32_t n_mels, int32_t mean_nor, void* stream);
+
+/* Sample-rate conversion in front of the Fbank: torchaudio.functional.resample with its defaults
+ * (Hann-windowed sinc, lowpass_filter_width 6, rolloff 0.99), the resampler behind the reference's
+ * load_audio (speakerlab/utils/fileio.py:105-129).  Rates are reduced by their gcd to o (orig) and
+ * n (new); every tap of the polyphase table is computed in double and rounded once to fp32; every
+ * output is one fp32 FMA chain in ascending tap order, so an utterance's result has the same bits
+ * alone and inside any batch.  Error codes of all three: a non-positive rate SPK_E_INVALID; equal
+ * rates SPK_E_INVALID from spk_resample_taps / spk_resample_f32 (nothing to resample;
+ * spk_resample_out_len returns L); a table above 8 MiB (n_phases * n_taps * 4 bytes, e.g. 44101 ->
+ * 16000) SPK_E_UNSUPPORTED from spk_resample_taps / spk_resample_f32. */
+/* ceil(new*L/orig) in gcd-reduced rates (torchaudio.functional.resample's output length). */
+int spk_resample_out_len(int64_t L, int32_t orig_freq, int32_t new_freq, int64_t* out_len);
+/* Polyphase tap table the kernel uses (diagnostics, tests; host memory, no GPU needed):
+ * n_phases = new/g, n_taps = 2*width + orig/g; taps (may be NULL to query sizes) [n_phases][n_taps]. */
+int spk_resample_taps(int32_t orig_freq, int32_t new_freq, int32_t* n_phases, int32_t* n_taps,
+                      int32_t* width, float* taps, size_t taps_len);
+/* Ragged batch: wav / out device float32, offsets DEVICE int64 [n_utt+1]; out_offsets[u+1]-out_offsets[u]
+ * must equal spk_resample_out_len of utterance u.  Enqueues only (the first call for a rate pair
+ * on a device builds and uploads its table, synchronously; later calls reuse it).  Samples before
+ * the first and past the last of an utterance read as zero; nothing outside the declared output
+ * ranges is written; the output buffer has the layout spk_fbank_f32 reads. */
+int spk_resample_f32(const float* wav, const int64_t* wav_offsets, int32_t n_utt, int32_t orig_freq,
+                     int32_t new_freq, float* out, const int64_t* out_offsets, void* stream);
 
 /* Build a handle on the CURRENT HIP device: folds BatchNorm into conv weights, packs them
  * for the kernels and uploads them (synchronous, once per model). */
