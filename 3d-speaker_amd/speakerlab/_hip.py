@@ -101,6 +101,9 @@ SYMBOLS = {
     'spk_cosine_topk': (ctypes.c_int, [_P, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_int32,
                                        ctypes.POINTER(spk_affinity_consumer_t), _P]),
     'spk_cosine_trials': (ctypes.c_int, [_P, _P, ctypes.c_int32, _P, _P, ctypes.c_int64, _P, _P]),
+    'spk_ahc_workspace_bytes': (ctypes.c_int, [ctypes.c_int64, ctypes.POINTER(ctypes.c_size_t)]),
+    'spk_ahc_average': (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int64, ctypes.c_float, _P, _P, _P,
+                                       ctypes.c_size_t, _P]),
 }
 
 _lib = None
@@ -606,3 +609,50 @@ def symmetric_eig(A: torch.Tensor):
         _check(lib().spk_symmetric_eig(A.data_ptr(), N, A.stride(0), w.data_ptr(), _stream(A.device)),
                'spk_symmetric_eig')
     return w, A
+
+
+# ----------------------------------------------------------------------------- AHC
+_ahc_ws: Dict = {}   # (device index, stream handle) -> workspace, grown on demand like the models'
+
+
+def ahc_workspace_bytes(n: int) -> int:
+    """Bytes of workspace ``spk_ahc_average`` needs for an n x n affinity (about 8 n^2: the fp64
+    working matrix); raises HipError with ``.code == E_UNSUPPORTED`` above the library's cap."""
+    nbytes = ctypes.c_size_t(0)
+    _check(lib().spk_ahc_workspace_bytes(int(n), ctypes.byref(nbytes)), 'spk_ahc_workspace_bytes')
+    return nbytes.value
+
+
+def ahc_average(S: torch.Tensor, threshold: float, return_count: bool = False):
+    """Average-linkage AHC of an N x N cosine affinity on the device: merge the two clusters with
+    the largest average similarity until it is below ``threshold`` (cluster.py:139-156).  Returns
+    int32 [N] device labels numbered by first occurrence (with ``return_count`` also the int32 [1]
+    device cluster count).  ``S`` may be a view with a row stride above N; it is not modified."""
+    require_device_tensor(S, 'ahc_average')
+    if S.dim() != 2 or S.shape[0] != S.shape[1]:
+        raise HipError(f'ahc_average: expected a square affinity, got {tuple(S.shape)}')
+    if S.dtype != torch.float32 or S.stride(1) != 1 or S.stride(0) < S.shape[0]:
+        S = S.to(torch.float32).contiguous()
+    N = S.shape[0]
+    dev = S.device if S.device.index is not None else torch.device('cuda', torch.cuda.current_device())
+    if N == 0:
+        out = torch.empty(0, dtype=torch.int32, device=dev)
+        return (out, torch.zeros(1, dtype=torch.int32, device=dev)) if return_count else out
+    need = ahc_workspace_bytes(N)
+    labels = torch.empty(N, dtype=torch.int32, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        key = (dev.index, _stream(dev))
+        ws = _ahc_ws.get(key)
+        if ws is None or ws.numel() < need:
+            ws = _ahc_ws.pop(key, None)   # free the old block before the larger one
+            del ws
+            ws = _ahc_ws[key] = torch.empty(need, dtype=torch.uint8, device=dev)
+        _check(lib().spk_ahc_average(S.data_ptr(), N, S.stride(0), float(threshold), labels.data_ptr(),
+                                     count.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)), 'spk_ahc_average')
+    return (labels, count) if return_count else labels
+
+
+def ahc_release_workspace():
+    """Drop the cached AHC workspaces (8 N^2 bytes of the largest N clustered per stream)."""
+    _ahc_ws.clear()

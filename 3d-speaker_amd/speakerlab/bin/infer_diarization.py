@@ -13,7 +13,7 @@ MI355X execution of the stages:
   sub-segment is circle-padded to the longest one by index arithmetic
   (``start + j mod len``), then GPU Fbank and the native ERes2NetV2 forward run on batches;
 * the N x N cosine affinity of the clustering runs on the GPU (MFMA), AHC / merging on the
-  host as in ``speakerlab.process.cluster``.
+  host as in ``speakerlab.process.cluster`` (``--gpu_ahc``: the AHC loop on the GPU too).
 
 Differences forced by the offline environment (documented in DESIGN.md):
 * TenVad (third-party binary library) is used when importable; otherwise an energy VAD
@@ -70,6 +70,9 @@ parser.add_argument('--synthetic_weights', action='store_true',
 parser.add_argument('--gpu_resample', action='store_true',
                     help='MI355X build: resample non-16 kHz input on the GPU (HIP windowed-sinc kernel) '
                          'instead of the host conv1d')
+parser.add_argument('--gpu_ahc', action='store_true',
+                    help='MI355X build: run the average-linkage AHC on the GPU as well (HIP kernels); the '
+                         'N x N affinity is never copied to the host')
 parser.add_argument('--vad', choices=['auto', 'ten_vad', 'energy'], default='auto',
                     help='MI355X build: VAD engine (TenVad when importable, else the energy stand-in)')
 
@@ -106,9 +109,10 @@ def get_speaker_embedding_model(device=None, cache_dir=None, synthetic_weights=F
     return model, FBank(80, sample_rate=16000, mean_nor=True)
 
 
-def get_cluster_backend(mer_cos=0.3, fix_cos_thr=0.3, min_cluster_size=0):
+def get_cluster_backend(mer_cos=0.3, fix_cos_thr=0.3, min_cluster_size=0, gpu_ahc=False):
     from speakerlab.process.cluster import CommonClustering
-    return CommonClustering('AHC', mer_cos=mer_cos, min_cluster_size=min_cluster_size, fix_cos_thr=fix_cos_thr)
+    kw = {'device': 'gpu'} if gpu_ahc else {}
+    return CommonClustering('AHC', mer_cos=mer_cos, min_cluster_size=min_cluster_size, fix_cos_thr=fix_cos_thr, **kw)
 
 
 class EnergyVad:
@@ -173,7 +177,7 @@ class Diarization3Dspeaker:
                  vad_energy_threshold=None, vad_boundary_expansion_ms=None, vad_boundary_energy_percentile=None,
                  vad_threshold=0.5, cluster_mer_cos=0.3, cluster_fix_cos_thr=0.3, cluster_min_cluster_size=0,
                  chunk_dur=1.5, chunk_step=0.75, batch_size=64, synthetic_weights=False, vad='auto', group=None,
-                 gpu_resample=False):
+                 gpu_resample=False, gpu_ahc=False):
         if include_overlap and hf_access_token is None:
             raise ValueError('hf_access_token is required when include_overlap is True.')
         if include_overlap:
@@ -186,7 +190,7 @@ class Diarization3Dspeaker:
         self.embedding_model, self.feature_extractor = get_speaker_embedding_model(
             self.device, model_cache_dir, synthetic_weights)
         self.vad_model = get_voice_activity_detection_model(self.device, model_cache_dir, vad_threshold, vad)
-        self.cluster = get_cluster_backend(cluster_mer_cos, cluster_fix_cos_thr, cluster_min_cluster_size)
+        self.cluster = get_cluster_backend(cluster_mer_cos, cluster_fix_cos_thr, cluster_min_cluster_size, gpu_ahc)
         self.batchsize = batch_size
         self.chunk_dur, self.chunk_step = chunk_dur, chunk_step
         self.fs = self.feature_extractor.sample_rate
@@ -310,6 +314,7 @@ class Diarization3Dspeaker:
             s, e = bounds[rank]
             block = _hip.cosine_affinity(X[s:e], X)
             S = all_gather_rows(block, [b - a for a, b in bounds], self.group)
+            # S is a device tensor: the host AHC copies it out, --gpu_ahc clusters it in place
             labels = self.cluster.from_affinity(embeddings, S, speaker_num=spk)
         speaker_num = labels.max() + 1
         segs = [[c[0], c[1], int(j)] for c, j in zip(chunks, labels)]
@@ -427,7 +432,7 @@ def main_process(rank, nprocs, args, wav_list, port=None):
         args.vad_boundary_expansion_ms, args.vad_boundary_energy_percentile, args.vad_threshold,
         args.cluster_mer_cos, args.cluster_fix_cos_thr, args.cluster_min_cluster_size, args.chunk_dur,
         args.chunk_step, args.batch_size, synthetic_weights=args.synthetic_weights, vad=args.vad, group=group,
-        gpu_resample=args.gpu_resample)
+        gpu_resample=args.gpu_resample, gpu_ahc=args.gpu_ahc)
     # one file per process, as the reference (:924); with --shard_chunks every rank takes part
     # in every file and rank 0 writes the outputs
     mine = wav_list if group is not None else wav_list[rank::nprocs]

@@ -7,6 +7,8 @@ MFMA); the decisions that follow stay on the host exactly as in the reference:
 * AHC (``cluster.py:139-156``): condensed(-S) -> average linkage (scipy's NN-chain
   implementation of the same Lance-Williams average linkage the reference gets from
   fastcluster, which is not installed here) -> shift by the minimum -> fcluster -1;
+  opt-in (``AHCluster(device='gpu')``): the same greedy average linkage on the device
+  (``spk_ahc_average``, csrc/ahc.hip), the affinity never copied to the host;
 * spectral (``cluster.py:23-112``): per-row p-pruning, symmetrisation, unnormalised
   Laplacian, ARPACK ``eigsh(which='SM')``, eigen-gap, sklearn ``k_means``;
 * ``filter_minor_cluster`` / ``merge_by_cos`` (``cluster.py:202-239``) on centroids.
@@ -50,6 +52,32 @@ def ahc_labels(S: np.ndarray, fix_cos_thr: float) -> np.ndarray:
     adjust = abs(lin[:, 2].min())
     lin[:, 2] += adjust
     return fcluster(lin, -fix_cos_thr + adjust, criterion='distance') - 1
+
+
+def _require_device(what: str):
+    import torch
+    from speakerlab import _hip
+    if not torch.cuda.is_available():
+        raise _hip.HipError(f'{what} runs on the ROCm device; none is available')
+
+
+def ahc_labels_gpu(S, fix_cos_thr: float) -> np.ndarray:
+    """``ahc_labels`` with the whole loop on the device (csrc/ahc.hip): the same flat clusters,
+    numbered by first occurrence (row 0's cluster is 0, the next new cluster 1, ...).  ``S`` is a
+    device tensor (it stays there: only the N int32 labels come back) or an ndarray.  An N above
+    the library's cap (``SPK_E_UNSUPPORTED``) is clustered by ``ahc_labels`` on the host."""
+    import torch
+    from speakerlab import _hip
+    _require_device('device AHC')
+    if not isinstance(S, torch.Tensor):
+        S = torch.from_numpy(np.ascontiguousarray(S, dtype=np.float32))
+    S = S.cuda()
+    try:
+        return _hip.ahc_average(S, fix_cos_thr).cpu().numpy()
+    except _hip.HipError as e:
+        if e.code != _hip.E_UNSUPPORTED:
+            raise
+        return ahc_labels(S.cpu().numpy(), fix_cos_thr)
 
 
 def pruned_count(n: int, pval: float, min_pnum: int) -> int:
@@ -187,13 +215,27 @@ class UmapHdbscan:
 
 
 class AHCluster:
-    def __init__(self, fix_cos_thr=0.4):
-        self.fix_cos_thr = fix_cos_thr
+    """``device='host'`` (default): the affinity is copied to the host and clustered by scipy, as
+    in the reference.  ``device='gpu'``: the linkage loop runs on the device too
+    (``ahc_labels_gpu``) and only the labels come back."""
+
+    def __init__(self, fix_cos_thr=0.4, device='host'):
+        if device not in ('host', 'gpu'):
+            raise ValueError("AHCluster: device must be 'host' or 'gpu', got %r" % (device,))
+        self.fix_cos_thr, self.device = fix_cos_thr, device
 
     def __call__(self, X, **kwargs):
+        if self.device == 'gpu':
+            import torch
+            from speakerlab import _hip
+            _require_device('device AHC')
+            t = torch.as_tensor(np.ascontiguousarray(X, dtype=np.float32)).cuda()
+            return ahc_labels_gpu(_hip.cosine_affinity(t), self.fix_cos_thr)
         return ahc_labels(cosine_affinity(X), self.fix_cos_thr)
 
     def from_affinity(self, S, **kwargs):
+        if self.device == 'gpu':
+            return ahc_labels_gpu(S, self.fix_cos_thr)
         return ahc_labels(S.cpu().numpy() if hasattr(S, 'cpu') else np.asarray(S), self.fix_cos_thr)
 
 
@@ -212,6 +254,7 @@ class CommonClustering:
             self.cluster = AHCluster(**kwargs)
         else:
             raise ValueError('%s is not currently supported.' % cluster_type)
+        # short inputs go to AHC: the AHC back-end itself (its device= included), else a default one
         self.cluster_for_short = self.cluster if cluster_type == 'AHC' else AHCluster()
 
     def __call__(self, X, **kwargs):

@@ -29,6 +29,8 @@
  *   spk_cosine_topk      the consumers of the row-block affinity: best matches
  *                        per row / threshold counts, the affinity never materialised
  *   spk_cosine_trials    the per-trial cosine_similarity loop of compute_score_metrics.py:102-118
+ *   spk_ahc_average      AHCluster.__call__ after the affinity, speakerlab/process/cluster.py:139-156
+ *                        (fastcluster linkage(method='average') + fcluster(criterion='distance'))
  */
 #ifndef SPK_HIP_H
 #define SPK_HIP_H
@@ -258,6 +260,25 @@ int spk_spectral_laplacian(const float* S, int64_t N, int64_t lds, int32_t n_ele
  * cluster.py:88-89): eigenvalues ascending into w (device, N), eigenvector k overwrites row
  * k of A (row-major, stride lda).  Synchronises the stream. */
 int spk_symmetric_eig(float* A, int64_t N, int64_t lda, float* w, void* stream);
+
+/* Average-linkage AHC of an N x N cosine affinity (reference cluster.py:139-156): the flat
+ * clusters fcluster(criterion='distance') cuts at -threshold, i.e. what is left when the two
+ * clusters with the largest average pairwise similarity are merged until that value is below
+ * threshold.  Ties go to the largest value, then the smallest row, then the smallest column; the
+ * merged cluster keeps the smaller index.  S (device, row stride lds >= N, only its upper
+ * triangle is read, like scipy's squareform) is not modified; labels (device, N) are numbered
+ * by first occurrence (row 0's cluster is 0, the next new cluster 1, ...) and n_clusters (device,
+ * 1) is their count.  N = 1 gives label 0.  The working matrix is fp64 and lives, with every other
+ * piece of state, in the caller's workspace (device, 8-byte aligned, spk_ahc_workspace_bytes:
+ * about 8 N^2 bytes).  Launches run on `stream`; the entry point synchronises it every 256 merge
+ * steps to read whether the loop has finished.
+ * Errors: N < 1, lds < N or a null pointer SPK_E_INVALID; a workspace below
+ * spk_ahc_workspace_bytes(N) SPK_E_WORKSPACE; N above the cap of 32768 (an 8 GiB matrix)
+ * SPK_E_UNSUPPORTED from both; a library built without the kernels SPK_E_UNSUPPORTED from
+ * spk_ahc_average.  Nothing is written on an error. */
+int spk_ahc_workspace_bytes(int64_t N, size_t* bytes);
+int spk_ahc_average(const float* S, int64_t N, int64_t lds, float threshold, int32_t* labels, int32_t* n_clusters,
+                    void* workspace, size_t workspace_bytes, void* stream);
 
 
 #ifdef __cplusplus
