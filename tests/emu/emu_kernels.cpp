@@ -67,7 +67,17 @@ static void emu_range_note(int* flag, float v) {   // common.h range guard: max 
 
 hipError_t launch_conv(const ConvDesc& d, hipStream_t) {
   EMU_GATE();
-  if (d.s0.cin % 4 || d.s0.ld % 4 || d.Kp % 16 || (d.osplit ? (d.osplit % 4 || d.ldo < d.osplit) : d.ldo < d.N) || d.K > d.Kp) return hipErrorInvalidValue;
+  // the clauses of the real launch_conv's host check (conv_gemm.hip).  More than one of s1 /
+  // addend / pre-activation is refused for every descriptor here; in the real library that
+  // refusal is launch_tile's, which such a descriptor reaches because the *_supported
+  // predicates of the halo, pointwise and LDS-DMA routes each exclude one of the pair
+  if (d.s0.cin % 4 || d.s0.ld % 4 || (d.s0.p2 && d.s0.ld2 % 4) || d.Kp % 32 ||
+      (d.osplit ? (d.osplit % 4 || d.ldo < d.osplit) : d.ldo < d.N) ||
+      (d.s1.p && (d.s1.cin % 4 || d.s1.ld % 4)) || d.N <= 0 || d.nimg <= 0 || d.Ho <= 0 || d.Wo <= 0 ||
+      (reinterpret_cast<uintptr_t>(d.s0.p) & 15) || (reinterpret_cast<uintptr_t>(d.w) & 15) || d.K > d.Kp ||
+      (d.ksplit > 1 && !d.partial))
+    return hipErrorInvalidValue;
+  if ((int)(d.s1.p != nullptr) + (int)(d.s0.p2 != nullptr) + (int)(d.s0.pre_scale != nullptr) > 1) return hipErrorInvalidValue;
   const int M = d.nimg * d.Ho * d.Wo;
   const int K0 = d.s0.kh * d.s0.kw * d.s0.cin;
   std::vector<float> a(d.Kp);
@@ -102,8 +112,16 @@ hipError_t launch_conv(const ConvDesc& d, hipStream_t) {
     }
     for (int n = 0; n < d.N; ++n) {
       const float* w = d.w + (size_t)n * d.Kp;
-      double acc = 0.0;
-      for (int k = 0; k < d.Kp; ++k) acc += (double)a[k] * w[k];
+      // four independent double chains (Kp is a multiple of 32): a serial one bounds the loop by
+      // the add latency, and the direct conv tests run shapes of a few GFLOP through here
+      double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+      for (int k = 0; k < d.Kp; k += 4) {
+        a0 += (double)a[k] * w[k];
+        a1 += (double)a[k + 1] * w[k + 1];
+        a2 += (double)a[k + 2] * w[k + 2];
+        a3 += (double)a[k + 3] * w[k + 3];
+      }
+      const double acc = (a0 + a1) + (a2 + a3);
       {
         const float o = epilogue(d, m, n, (float)acc);
         emu_range_note(d.range_flag, o);
