@@ -267,7 +267,7 @@ void build_campplus(Builder& b, int T) {
         b.writes({{GATE, Builder::AUX}, {SEGSUM, Builder::AUX}}).step(c + ".gate", [=](const Ctx& cx) {
           return launch_cam_gate(cx.resolve(Hh), B, T2, bnc, bnc, 100, nseg, w1, k1p, b1, red, w2, k2p, b2, growth,
                                  cx.resolve(GATE), growth, cx.resolve(SEGSUM), cx.stream, cx.resolve_i(LEN2));
-        }, "cam_gate_kernel", 4.0 * B * T2 * bnc);
+        }, cam_gate_kernel_name(B, bnc, bnc, nseg, w1, k1p, red, w2, k2p, growth), 4.0 * B * T2 * bnc);
       }
       {
         const A4 hh{Hh, bnc, 1, T2, bnc};

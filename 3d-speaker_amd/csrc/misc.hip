@@ -36,7 +36,7 @@ stem_conv3x3_kernel(const float* __restrict__ feats, int B, int T, int F, const 
   const int ntt = (T + STEM_ST - 1) / STEM_ST, nft = (F + STEM_SF - 1) / STEM_SF;
   const int b = blockIdx.x / (nft * ntt), r = blockIdx.x % (nft * ntt);
   const int f0 = (r / ntt) * STEM_SF, t0 = (r % ntt) * STEM_ST;
-  const int Tb = vlen ? vlen[b] : T;                 // ragged batches: frames past Tb are padding
+  const int Tb = vlen ? min(vlen[b], T) : T;         // ragged batches: frames past Tb are padding
   for (int i = threadIdx.x; i < WF * WT; i += blockDim.x) {
     const int ff = f0 - 1 + i % WF, tt = t0 - 1 + i / WF;   // f fastest: the rows are [t][F]
     win[(i % WF) * WT + i / WF] = (ff >= 0 && ff < F && tt >= 0 && tt < Tb) ? feats[((size_t)b * T + tt) * F + ff] : 0.f;
@@ -98,12 +98,16 @@ tstp_kernel(const float* __restrict__ x, int B, int H, int W, int C, int ld, flo
     const int b = (int)(e / ((long long)C * H));
     const float* p = x + ((size_t)(b * H + h) * W) * ld + c;
     // one Welford pass (mean, M2): the activation is read once, not twice
-    float mean = 0.f, q = 0.f;
+    // on x - x[0]: with |mean| >> std the running mean of x itself is rounded at ulp(mean)
+    float mean = 0.f, q = 0.f, x0 = 0.f;
     scan_frames<16>(p, ld, W, [&](float v, int t) {
-      const float dlt = v - mean;
+      if (t == 0) x0 = v;
+      const float xs = v - x0;
+      const float dlt = xs - mean;
       mean += dlt / (float)(t + 1);
-      q = fmaf(dlt, v - mean, q);
+      q = fmaf(dlt, xs - mean, q);
     });
+    mean += x0;
     const float var = q / (float)(unbiased ? W - 1 : W);
     // parts: bit 0 = mean (TAP), bit 1 = std (TSDP); TSTP = both, mean first
     const int np = (parts & 1) + ((parts >> 1) & 1);
@@ -139,11 +143,15 @@ astp_pool_kernel(const float* __restrict__ logit, int ldl, const float* __restri
         m2 *= sc;
         mx = lv;
       }
-      const float w = __expf(lv - mx);
+      const float w = __expf(lv - mx), sw0 = sw;
       sw += w;
-      const float d = xv - mean;
-      mean += d * (w / sw);
-      m2 += w * d * (xv - mean);
+      const float d = xv - mean, r = w / sw;
+      // the new mean from the nearer end (mean + d r = xv - d q, q = sw0 / sw), and
+      // w d (xv - new mean) with xv - new mean = d q written out: when a heavy frame follows
+      // light ones (r -> 1), mean + d rounds at ulp(d) and the difference cancels to rounding noise
+      const float q = sw0 / sw;
+      mean = r > 0.5f ? fmaf(-d, q, xv) : fmaf(d, r, mean);
+      m2 += w * q * d * d;
     }
     float* o = out + (size_t)b * 2 * F * C;
     o[f * C + c] = mean;
@@ -165,7 +173,7 @@ hipError_t launch_stem_conv3x3(const float* feats, int B, int T, int F, const fl
                                int act, int wstride, float* out, int ldo, hipStream_t s, const int* vlen,
                                int* range_flag) {
   // cout / 4 channel quads must divide the 256 threads (one quad per thread for every pixel)
-  if (cout % 4 || cout > 128 || 256 % (cout / 4) || ldo % 4 || (long long)B * F * T * ldo >= (1LL << 40))
+  if (cout <= 0 || cout % 4 || cout > 128 || 256 % (cout / 4) || ldo % 4 || (long long)B * F * T * ldo >= (1LL << 40))
     return hipErrorInvalidValue;
   const long long blocks = (long long)B * ((F + STEM_SF - 1) / STEM_SF) * ((T + STEM_ST - 1) / STEM_ST);
   if (blocks >= (1LL << 31)) return hipErrorInvalidValue;

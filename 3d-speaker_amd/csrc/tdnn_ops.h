@@ -1,5 +1,6 @@
 #pragma once
 #include <algorithm>
+#include <string>
 #include "common.h"
 
 namespace spk {
@@ -24,6 +25,23 @@ hipError_t launch_cam_context(const float* x, int B, int T, int C, int ld, int s
 hipError_t launch_cam_gate(const float* x, int B, int T, int C, int ld, int seg, int nseg, const float* w1, int k1p,
                           const float* b1, int red, const float* w2, int k2p, const float* b2, int growth, float* gate,
                           int ldg, float* segsum, hipStream_t s, const int* vlen = nullptr);
+// Which kernels serve a gate shape (cam_gate_route.cpp): host arithmetic on the shape alone,
+// the one predicate launch_cam_gate, cam_gate_kernel_name and the host emulation share.
+constexpr int CAM_SEGS = 4;   // segments whose 1x1 layers run together (weights read once)
+constexpr int CAM_WQ = 8;     // lean gate: float4 quads of a thread's weight slice per layer
+enum CamRoute { CAM_REFUSED, CAM_FUSED, CAM_PAIR_LEAN, CAM_PAIR_LDS };
+struct CamPick {
+  CamRoute route;
+  size_t lds;   // dynamic LDS bytes of the gate kernel
+};
+CamPick cam_gate_pick(int B, int C, int ld, int nseg, const float* w1, int k1p, int red, const float* w2, int k2p,
+                      int growth);
+// the kernel(s) launch_cam_gate runs for this shape: "cam_gate_fused_kernel",
+// "cam_segsum_kernel+cam_gate_lean_kernel" or "cam_segsum_kernel+cam_gate_kernel" ("" for a
+// shape it refuses), from cam_gate_pick.  A weak definition: the host emulation, which has
+// one gate for every route, may give its own name
+std::string cam_gate_kernel_name(int B, int C, int ld, int nseg, const float* w1, int k1p, int red, const float* w2,
+                                 int k2p, int growth);
 hipError_t launch_stats_pool(const float* x, int B, int T, int C, int ld, float* out, hipStream_t s,
                              const int* vlen = nullptr);
 // out[b] = (in[b] + 2 pad - k) / stride + 1 (valid frames after a strided conv)

@@ -18,14 +18,12 @@ namespace spk {
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-constexpr int CAM_SEGS = 4;   // segments whose 1x1 layers run together (weights read once)
-constexpr int CAM_WQ = 8;
 #ifndef SPK_SEGSUM_U
 #define SPK_SEGSUM_U 4   // cam_segsum: row loads in flight per thread
 #endif
 #ifndef SPK_ATTN_U
 #define SPK_ATTN_U 8     // attn_pool: frames per load batch
-#endif     // lean gate: float4 quads of a thread's weight slice per layer
+#endif
 
 inline int grid_for(long long n) { return (int)std::min<long long>((n + 255) / 256, 65536); }
 
@@ -58,14 +56,18 @@ __global__ void asp_stats_kernel(const float* __restrict__ x, int B, int T, int 
     const int c = (int)(e % C), b = (int)(e / C);
     const int Tb = valid_frames(vlen, b, T);
     const float* p = x + (size_t)b * T * ld + c;
-    // one Welford pass (mean, M2) instead of two passes over x; var = M2 / T
-    float mean = 0.f, m2 = 0.f;
+    // one Welford pass (mean, M2) instead of two passes over x; var = M2 / T.  The pass runs on
+    // x - x[0]: with |mean| >> std the running mean of x itself is rounded at ulp(mean), which
+    // is what the deviations are measured against
+    float mean = 0.f, m2 = 0.f, x0 = 0.f;
     scan_frames<16>(p, ld, Tb, [&](float xv, int t) {
-      const float d = xv - mean;
+      if (t == 0) x0 = xv;
+      const float xs = xv - x0;
+      const float d = xs - mean;
       mean += d / (float)(t + 1);
-      m2 += d * (xv - mean);
+      m2 += d * (xs - mean);
     });
-    out[(size_t)b * 2 * C + c] = mean;
+    out[(size_t)b * 2 * C + c] = x0 + mean;
     out[(size_t)b * 2 * C + C + c] = sqrtf(fmaxf(m2 / (float)Tb, eps));
   }
 }
@@ -90,11 +92,15 @@ __global__ void attn_pool_kernel(const float* __restrict__ logit, int ldl, const
         m2 *= sc;
         mx = lv;
       }
-      const float w = __expf(lv - mx);
+      const float w = __expf(lv - mx), sw0 = sw;
       sw += w;
-      const float d = xv - mean;
-      mean += d * (w / sw);
-      m2 += w * d * (xv - mean);
+      const float d = xv - mean, r = w / sw;
+      // the new mean from the nearer end (mean + d r = xv - d q, q = sw0 / sw), and
+      // w d (xv - new mean) with xv - new mean = d q written out: when a heavy frame follows
+      // light ones (r -> 1), mean + d rounds at ulp(d) and the difference cancels to rounding noise
+      const float q = sw0 / sw;
+      mean = r > 0.5f ? fmaf(-d, q, xv) : fmaf(d, r, mean);
+      m2 += w * q * d * d;
     });
     out[(size_t)b * 2 * C + c] = mean;
     out[(size_t)b * 2 * C + C + c] = sqrtf(fmaxf(m2 / sw, eps));
@@ -391,13 +397,15 @@ __global__ void stats_pool_kernel(const float* __restrict__ x, int B, int T, int
     const int c = (int)(e % C), b = (int)(e / C);
     const int Tb = valid_frames(vlen, b, T);
     const float* p = x + (size_t)b * T * ld + c;
-    float mean = 0.f, q = 0.f;                       // one Welford pass (mean, M2)
+    float mean = 0.f, q = 0.f, x0 = 0.f;             // one Welford pass (mean, M2) on x - x[0] (asp_stats)
     scan_frames<16>(p, ld, Tb, [&](float v, int t) {
-      const float d = v - mean;
+      if (t == 0) x0 = v;
+      const float xs = v - x0;
+      const float d = xs - mean;
       mean += d / (float)(t + 1);
-      q += d * (v - mean);
+      q += d * (xs - mean);
     });
-    out[(size_t)b * 2 * C + c] = mean;
+    out[(size_t)b * 2 * C + c] = x0 + mean;
     out[(size_t)b * 2 * C + C + c] = sqrtf(q / (float)(Tb - 1));
   }
 }
@@ -450,34 +458,21 @@ hipError_t launch_cam_context(const float* x, int B, int T, int C, int ld, int s
 hipError_t launch_cam_gate(const float* x, int B, int T, int C, int ld, int seg, int nseg, const float* w1, int k1p,
                           const float* b1, int red, const float* w2, int k2p, const float* b2, int growth, float* gate,
                           int ldg, float* segsum, hipStream_t s, const int* vlen) {
-  if (C % 4 || C / 4 > 256 || ld % 4 || red <= 0 || red > 1024 || growth <= 0 || growth > 1024 || B <= 0 || nseg <= 0)
-    return hipErrorInvalidValue;
-  static const bool lean_off = std::getenv("SPK_CAM_GATE_LDS") != nullptr;   // A/B: the transposing kernel
-  static const bool fuse_off = std::getenv("SPK_CAM_GATE_PAIR") != nullptr;  // A/B: segment sums as their own launch
-  // the lean kernel's butterfly sums Q = 256 / red (or 256 / growth) adjacent lanes with
-  // __shfl_xor, i.e. within one wave only when Q <= 64
-  const bool lean = !lean_off && red >= 4 && growth >= 4 && 256 % red == 0 && 256 % growth == 0 && C % (4 * (256 / red)) == 0 &&
-                    red % (4 * (256 / growth)) == 0 && C / (256 / red) <= 4 * CAM_WQ &&
-                    red / (256 / growth) <= 4 * CAM_WQ && k1p % 4 == 0 && k2p % 4 == 0 &&
-                    (reinterpret_cast<uintptr_t>(w1) & 15) == 0 && (reinterpret_cast<uintptr_t>(w2) & 15) == 0;
-  const size_t lds_f = sizeof(float) * (4 * 256 + (size_t)nseg * C + C + CAM_SEGS * ((size_t)C + red));
-  if (lean && !fuse_off && lds_f <= 64 * 1024) {
-    hipLaunchKernelGGL(cam_gate_fused_kernel, dim3(B), dim3(256), lds_f, s, x, T, C, ld, seg, nseg, w1, k1p, b1, red,
+  const CamPick pick = cam_gate_pick(B, C, ld, nseg, w1, k1p, red, w2, k2p, growth);
+  if (pick.route == CAM_REFUSED) return hipErrorInvalidValue;
+  if (pick.route == CAM_FUSED) {
+    hipLaunchKernelGGL(cam_gate_fused_kernel, dim3(B), dim3(256), pick.lds, s, x, T, C, ld, seg, nseg, w1, k1p, b1, red,
                        w2, k2p, b2, growth, gate, ldg, vlen, launch_gate());
     return hipGetLastError();
   }
   hipLaunchKernelGGL(cam_segsum_kernel, dim3(nseg, B), dim3(256), 0, s, x, T, C, ld, seg, nseg, segsum, vlen, launch_gate());
   if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-  if (lean) {
-    const size_t lds_l = sizeof(float) * ((size_t)C + CAM_SEGS * ((size_t)C + red));
-    hipLaunchKernelGGL(cam_gate_lean_kernel, dim3(B), dim3(256), lds_l, s, segsum, T, C, seg, nseg, w1, k1p, b1, red,
+  if (pick.route == CAM_PAIR_LEAN) {
+    hipLaunchKernelGGL(cam_gate_lean_kernel, dim3(B), dim3(256), pick.lds, s, segsum, T, C, seg, nseg, w1, k1p, b1, red,
                        w2, k2p, b2, growth, gate, ldg, vlen, launch_gate());
     return hipGetLastError();
   }
-  const size_t lds = sizeof(float) * ((size_t)C * (red + 1) + (size_t)red * (growth + 1) + C +
-                                      CAM_SEGS * (C + red + 1024));
-  if (lds > 64 * 1024) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(cam_gate_kernel, dim3(B), dim3(1024), lds, s, segsum, T, C, seg, nseg, w1, k1p, b1, red, w2, k2p,
+  hipLaunchKernelGGL(cam_gate_kernel, dim3(B), dim3(1024), pick.lds, s, segsum, T, C, seg, nseg, w1, k1p, b1, red, w2, k2p,
                      b2, growth, gate, ldg, vlen, launch_gate());
   return hipGetLastError();
 }

@@ -140,7 +140,12 @@ bool aff_x3_supported(int cp, int nmid) { return (nmid == 32 || nmid == 64) && c
 std::string aff_x3_kernel_name(int, int nmid) { return "emu_aff<" + std::to_string(nmid / 32) + ">"; }
 hipError_t launch_aff_x3(const AffDesc& a, hipStream_t) {
   EMU_GATE();
-  if (!aff_x3_supported(a.cp, a.nmid) || a.kp1 < 2 * a.cp || a.kp2 < a.nmid) return hipErrorInvalidValue;
+  // the clauses of the real launch's host check (aff.hip), the fp32 matrices in place of the planes
+  if (!aff_x3_supported(a.cp, a.nmid) || a.M <= 0 || !a.w1 || !a.w2 || !a.b1 || !a.b2 || a.kp1 < 2 * a.cp ||
+      a.kp1 % 8 || a.kp2 < a.nmid || a.kp2 % 4 || a.ldx % 4 || a.ldy % 4 || a.ldo % 4 || a.ldx < a.cp ||
+      a.ldy < a.cp || a.ldo < a.cp || (reinterpret_cast<uintptr_t>(a.x) & 15) ||
+      (reinterpret_cast<uintptr_t>(a.y) & 15) || (reinterpret_cast<uintptr_t>(a.out) & 15))
+    return hipErrorInvalidValue;
   std::vector<double> h(a.nmid);
   for (int m = 0; m < a.M; ++m) {
     const float* x = a.x + (size_t)m * a.ldx;
@@ -158,14 +163,44 @@ hipError_t launch_aff_x3(const AffDesc& a, hipStream_t) {
       for (int j = 0; j < a.nmid; ++j) acc += (double)w[j] * h[j];
       const float t = 1.0f + std::tanh((float)acc);
       a.out[(size_t)m * a.ldo + n] = x[n] * t + y[n] * (2.0f - t);
+      emu_range_note(a.range_flag, a.out[(size_t)m * a.ldo + n]);
     }
   }
   return hipSuccess;
 }
 
-// the emulated GEMM reads the fp32 weights; the split planes are not needed on the host
-hipError_t launch_split_f16(const float*, uint16_t*, uint16_t*, size_t, hipStream_t) {
-  EMU_GATE(); return hipSuccess; }
+// fp32 -> fp16 bits, round to nearest even (overflow to inf, subnormals, NaN kept), and back
+static uint16_t f2h(float f) {
+  uint32_t u;
+  std::memcpy(&u, &f, 4);
+  const uint32_t sign = (u >> 16) & 0x8000u, a = u & 0x7FFFFFFFu;
+  if (a >= 0x7F800000u) return (uint16_t)(sign | 0x7C00u | (a > 0x7F800000u ? 0x200u : 0u));
+  if (a >= 0x477FF000u) return (uint16_t)(sign | 0x7C00u);          // rounds to 2^16 or above
+  if (a < 0x33000000u) return (uint16_t)sign;                       // below half the smallest subnormal
+  const int e = (int)(a >> 23) - 127;
+  uint32_t man = (a & 0x7FFFFFu) | 0x800000u;                       // 24 bits
+  const int shift = e >= -14 ? 13 : 13 + (-14 - e);                 // bits dropped
+  const uint32_t keep = man >> shift, rem = man & ((1u << shift) - 1), half = 1u << (shift - 1);
+  uint32_t r = keep + ((rem > half || (rem == half && (keep & 1))) ? 1u : 0u);
+  // normal: keep carries the implicit bit (1 << 10), the exponent field adds up on a carry
+  const uint32_t bits = e >= -14 ? ((uint32_t)(e + 14) << 10) + r : r;
+  return (uint16_t)(sign | bits);
+}
+static float h2f(uint16_t h) {
+  const int e = (h >> 10) & 31, m = h & 1023;
+  const float v = e == 31 ? (m ? NAN : INFINITY)
+                           : e == 0 ? std::ldexp((float)m, -24) : std::ldexp((float)(m | 1024), e - 25);
+  return (h & 0x8000) ? -v : v;
+}
+// the emulated GEMMs read the fp32 weights; the planes are written all the same (the
+// arithmetic of misc.hip split_f16_kernel), for the direct test of the split
+hipError_t launch_split_f16(const float* w, uint16_t* hi, uint16_t* lo, size_t n, hipStream_t) {
+  for (size_t i = 0; i < n; ++i) {
+    hi[i] = f2h(w[i]);
+    lo[i] = f2h((w[i] - h2f(hi[i])) * 2048.0f);
+  }
+  return hipSuccess;
+}
 // nor the fragment-order copy of the LDS-DMA GEMM (conv_gemm_f.hip)
 size_t frag_halves(int N, int Kp) { return (size_t)Kp * (size_t)((N + 255) / 256 * 256) * 2; }
 hipError_t launch_pack_frag(const uint16_t*, const uint16_t*, int, int, uint16_t*, hipStream_t) { return hipSuccess; }
@@ -178,6 +213,7 @@ hipError_t launch_word_reset(int* w, hipStream_t) {
 
 hipError_t launch_range_check(const float* x, size_t n, int* flag, hipStream_t) {
   EMU_GATE();
+  if (!flag) return hipSuccess;
   for (size_t i = 0; i < n; ++i) emu_range_note(flag, x[i]);
   return hipSuccess;
 }
@@ -185,8 +221,9 @@ hipError_t launch_range_check(const float* x, size_t n, int* flag, hipStream_t) 
 hipError_t launch_stem_conv3x3(const float* feats, int B, int T, int F, const float* w, const float* bias, int cout,
                                int act, int wstride, float* out, int ldo, hipStream_t, const int* vlen, int* range_flag) {
   EMU_GATE();
+  if (cout <= 0 || cout % 4 || cout > 128 || 256 % (cout / 4) || ldo % 4) return hipErrorInvalidValue;
   for (int b = 0; b < B; ++b) {
-    const int Tb = vlen ? vlen[b] : T;
+    const int Tb = vlen ? std::min(vlen[b], T) : T;
     for (int f = 0; f < F; ++f)
       for (int t = 0; t < T; ++t)
         for (int c = 0; c < cout; ++c) {
@@ -208,6 +245,7 @@ hipError_t launch_stem_conv3x3(const float* feats, int B, int T, int F, const fl
 hipError_t launch_tstp(const float* x, int B, int H, int W, int C, int ld, float eps, int unbiased, float* out,
                        hipStream_t, int parts) {
   EMU_GATE();
+  if (parts < 1 || parts > 3) return hipErrorInvalidValue;
   const int np = (parts & 1) + ((parts >> 1) & 1);
   for (int b = 0; b < B; ++b)
     for (int h = 0; h < H; ++h)
@@ -270,12 +308,15 @@ bool res2_block_supported(const Res2Desc& d) {
   const bool st2 = d.stride == 2 && (hin - 1) / 2 + 1 == d.H && (win - 1) / 2 + 1 == d.W;
   const bool s1 = st1 && (d.proj ? (d.C == 64 && co == 128) : (d.C == 128 && co == 128)) && d.width >= 1 && d.width <= 32;
   const bool s2 = (d.proj ? (st2 && d.C == 128) : (st1 && d.C == 256)) && co == 256 && d.width > 32 && d.width <= 64;
-  return (s1 || s2) && d.w1 && d.wa && d.wb && d.w3 && d.b1 && d.ba && d.bb && d.b3;
+  return (s1 || s2) && d.nimg > 0 && d.H > 0 && d.W > 0 && d.w1 && d.wa && d.wb && d.w3 && d.b1 && d.ba && d.bb && d.b3;
 }
 std::string res2_block_kernel_name(const Res2Desc& d) { return "emu_res2_block<" + std::to_string(d.C) + ">"; }
 hipError_t launch_res2_block(const Res2Desc& d, hipStream_t) {
   EMU_GATE();
-  if (!res2_block_supported(d) || d.x == d.out) return hipErrorInvalidValue;
+  // the planes are not read here, but the real host check refuses a descriptor without them
+  if (!res2_block_supported(d) || d.x == d.out || !d.w1h || !d.w1l || !d.wah || !d.wal || !d.wbh || !d.wbl || !d.w3h ||
+      !d.w3l)
+    return hipErrorInvalidValue;
   const int SW = d.width <= 32 ? 32 : 64;
   const int H = d.H, W = d.W, C = d.C, CO = d.Cout ? d.Cout : d.C, K3 = d.proj ? 2 * SW + C : 2 * SW;
   const int S = d.stride, Hin = d.Hin ? d.Hin : H, Win = d.Win ? d.Win : W;
@@ -450,6 +491,7 @@ hipError_t launch_attn_pool(const float* l, int ldl, const float* x, int ldx, in
 hipError_t launch_se_apply(const float* x, int ldx, const float* g, int ldg, const float* r, int ldr, float* out,
                            int ldo, int B, int T, int C, hipStream_t, int* range_flag) {
   EMU_GATE();
+  if (C % 4 || ldx % 4 || ldg % 4 || ldr % 4 || ldo % 4) return hipErrorInvalidValue;
   for (int b = 0; b < B; ++b)
     for (int t = 0; t < T; ++t)
       for (int c = 0; c < C; ++c) {
@@ -459,10 +501,16 @@ hipError_t launch_se_apply(const float* x, int ldx, const float* g, int ldg, con
       }
   return hipSuccess;
 }
+// one gate for every route: the shapes the real launch accepts are cam_gate_pick's (shared, cam_gate_route.cpp)
+std::string cam_gate_kernel_name(int B, int C, int ld, int nseg, const float* w1, int k1p, int red, const float* w2,
+                                 int k2p, int growth) {
+  return cam_gate_pick(B, C, ld, nseg, w1, k1p, red, w2, k2p, growth).route == CAM_REFUSED ? "" : "emu_cam_gate";
+}
 hipError_t launch_cam_gate(const float* x, int B, int T, int C, int ld, int seg, int nseg, const float* w1, int k1p,
                           const float* b1, int red, const float* w2, int k2p, const float* b2, int growth, float* gate,
                           int ldg, float*, hipStream_t, const int* vlen) {
   EMU_GATE();
+  if (cam_gate_kernel_name(B, C, ld, nseg, w1, k1p, red, w2, k2p, growth).empty()) return hipErrorInvalidValue;
   std::vector<double> ctx(C), h(red);
   for (int b = 0; b < B; ++b) {
     const int Tb = vlen ? std::min(std::max(vlen[b], 1), T) : T;
@@ -492,7 +540,7 @@ hipError_t launch_cam_context(const float* x, int B, int T, int C, int ld, int s
                               hipStream_t, const int* vlen) {
   EMU_GATE();
   for (int b = 0; b < B; ++b) {
-    const int Tb = vlen ? vlen[b] : T;
+    const int Tb = vframes(vlen, b, T);
     for (int c = 0; c < C; ++c) {
       double tot = 0;
       for (int t = 0; t < Tb; ++t) tot += x[((size_t)b * T + t) * ld + c];
@@ -509,7 +557,7 @@ hipError_t launch_cam_context(const float* x, int B, int T, int C, int ld, int s
 hipError_t launch_stats_pool(const float* x, int B, int T, int C, int ld, float* out, hipStream_t, const int* vlen) {
   EMU_GATE();
   for (int b = 0; b < B; ++b) {
-    const int Tb = vlen ? vlen[b] : T;
+    const int Tb = vframes(vlen, b, T);
     for (int c = 0; c < C; ++c) {
       double s = 0, q = 0;
       for (int t = 0; t < Tb; ++t) s += x[((size_t)b * T + t) * ld + c];
