@@ -12,6 +12,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "cosine_pair.h"
 
 namespace spk {
 
@@ -269,34 +270,16 @@ __global__ void cosine_topk_merge_kernel(long long Na, TopkArgs t, float* __rest
 }
 
 // Trial gather (compute_score_metrics.py:102-118): score[t] = cos(Ea[ia[t]], Eb[ib[t]]), one
-// wave per trial, float4 per lane, the three sums reduced across the wave.  O(T * E) instead of
-// the Ne x Nt affinity the reference's per-trial sklearn calls amount to.
+// wave per trial (wave_pair_cosine, cosine_pair.h).  O(T * E) instead of the Ne x Nt affinity the
+// reference's per-trial sklearn calls amount to.
 __global__ void __launch_bounds__(256)
 cosine_trials_kernel(const float* __restrict__ A, const float* __restrict__ Bm, int E, const long long* __restrict__ ia,
                      const long long* __restrict__ ib, long long T, float* __restrict__ out) {
   const long long tr = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (tr >= T) return;
-  const float* a = A + ia[tr] * E;
-  const float* b = Bm + ib[tr] * E;
-  float d = 0.f, na = 0.f, nb = 0.f;
-  for (int k = lane * 4; k < E; k += 256) {
-    const f32x4 x = *reinterpret_cast<const f32x4*>(a + k);
-    const f32x4 y = *reinterpret_cast<const f32x4*>(b + k);
-    d += x[0] * y[0] + x[1] * y[1] + x[2] * y[2] + x[3] * y[3];
-    na += x[0] * x[0] + x[1] * x[1] + x[2] * x[2] + x[3] * x[3];
-    nb += y[0] * y[0] + y[1] * y[1] + y[2] * y[2] + y[3] * y[3];
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    d += __shfl_xor(d, o, 64);
-    na += __shfl_xor(na, o, 64);
-    nb += __shfl_xor(nb, o, 64);
-  }
-  if (lane == 0) {
-    const float sa = na == 0.f ? 1.f : sqrtf(na), sb = nb == 0.f ? 1.f : sqrtf(nb);
-    out[tr] = d / (sa * sb);
-  }
+  const float s = wave_pair_cosine(A + ia[tr] * E, Bm + ib[tr] * E, E, lane);
+  if (lane == 0) out[tr] = s;
 }
 
 }  // namespace

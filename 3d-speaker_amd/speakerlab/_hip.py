@@ -104,6 +104,13 @@ SYMBOLS = {
     'spk_ahc_workspace_bytes': (ctypes.c_int, [ctypes.c_int64, ctypes.POINTER(ctypes.c_size_t)]),
     'spk_ahc_average': (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int64, ctypes.c_float, _P, _P, _P,
                                        ctypes.c_size_t, _P]),
+    'spk_topk_stats': (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, _P, _P, _P]),
+    'spk_cosine_cohort_stats_workspace_bytes': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64,
+                                                               ctypes.POINTER(ctypes.c_size_t),
+                                                               ctypes.POINTER(ctypes.c_size_t)]),
+    'spk_cosine_cohort_stats': (ctypes.c_int, [_P, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                               _P, _P, _P, ctypes.c_size_t, _P]),
+    'spk_cosine_trials_norm': (ctypes.c_int, [_P, _P, ctypes.c_int32, _P, _P, ctypes.c_int64, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None
@@ -656,3 +663,119 @@ def ahc_average(S: torch.Tensor, threshold: float, return_count: bool = False):
 def ahc_release_workspace():
     """Drop the cached AHC workspaces (8 N^2 bytes of the largest N clustered per stream)."""
     _ahc_ws.clear()
+
+
+# ----------------------------------------------------------------------------- score normalisation
+_cohort_ws: Dict = {}   # (device index, stream handle) -> workspace, grown on demand like the AHC's
+
+
+def _dev_of(t: torch.Tensor) -> torch.device:
+    return t.device if t.device.index is not None else torch.device('cuda', torch.cuda.current_device())
+
+
+def topk_stats(S: torch.Tensor, k: int, out=None):
+    """(mean, std) float32 [rows] device tensors: mean and population standard deviation (ddof 0)
+    of the ``k`` largest entries of every row of ``S`` (spk_topk_stats; exact selection, ties
+    across the cut cannot change the result, the same input gives the same bits).  ``S`` may be a
+    view with a row stride above its width: only its own columns are read.  ``out``: a (mean, std)
+    pair of contiguous float32 [rows] device tensors (or views) to write into."""
+    require_device_tensor(S, 'topk_stats')
+    if S.dim() != 2:
+        raise HipError(f'topk_stats: expected a matrix, got {tuple(S.shape)}')
+    rows, cols = S.shape
+    if S.dtype != torch.float32 or (cols > 1 and S.stride(1) != 1) or (rows > 1 and S.stride(0) < cols):
+        S = S.to(torch.float32).contiguous()
+    lds = S.stride(0) if rows > 1 else max(cols, 1)
+    dev = _dev_of(S)
+    if out is None:
+        mean = torch.empty(rows, dtype=torch.float32, device=dev)
+        std = torch.empty(rows, dtype=torch.float32, device=dev)
+    else:
+        mean, std = out
+        for t in (mean, std):
+            require_device_tensor(t, 'topk_stats')
+            if t.dtype != torch.float32 or t.shape != (rows,) or not t.is_contiguous():
+                raise HipError('topk_stats: out must be two contiguous float32 [rows] tensors')
+    with torch.cuda.device(dev):
+        _check(lib().spk_topk_stats(S.data_ptr(), rows, cols, lds, int(k), mean.data_ptr(), std.data_ptr(),
+                                    _stream(dev)), 'spk_topk_stats')
+    return mean, std
+
+
+def cosine_cohort_stats_workspace_bytes(n: int, nc: int):
+    """(smallest, recommended) workspace bytes of ``spk_cosine_cohort_stats`` for n rows against a
+    cohort of nc: one block of 128 rows of scores, and blocks of about 128 MiB."""
+    lo, rec = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    _check(lib().spk_cosine_cohort_stats_workspace_bytes(int(n), int(nc), ctypes.byref(lo), ctypes.byref(rec)),
+           'spk_cosine_cohort_stats_workspace_bytes')
+    return lo.value, rec.value
+
+
+def cosine_cohort_stats(x: torch.Tensor, cohort: torch.Tensor, k: int, workspace_bytes: Optional[int] = None):
+    """(mean, std) float32 [N] device tensors of the ``k`` best cosine scores of every row of ``x``
+    [N, E] against ``cohort`` [Nc, E] (spk_cosine_cohort_stats): the affinity is produced and
+    reduced in row blocks inside a cached workspace, never as a whole.  ``workspace_bytes`` overrides
+    the recommended workspace size (any size from the smallest up gives the same bits)."""
+    require_device_tensor(x, 'cosine_cohort_stats')
+    require_device_tensor(cohort, 'cosine_cohort_stats')
+    if x.dim() != 2 or cohort.dim() != 2 or x.shape[1] != cohort.shape[1]:
+        raise HipError(f'cosine_cohort_stats: expected [N, E] and [Nc, E], got {tuple(x.shape)} and '
+                       f'{tuple(cohort.shape)}')
+    dev = _dev_of(x)
+    x = x.to(torch.float32).contiguous()
+    cohort = cohort.to(device=dev, dtype=torch.float32).contiguous()
+    N, Nc, E = x.shape[0], cohort.shape[0], x.shape[1]
+    mean = torch.empty(N, dtype=torch.float32, device=dev)
+    std = torch.empty(N, dtype=torch.float32, device=dev)
+    if N == 0:
+        return mean, std
+    need = cosine_cohort_stats_workspace_bytes(N, Nc)[1] if workspace_bytes is None else int(workspace_bytes)
+    with torch.cuda.device(dev):
+        key = (dev.index, _stream(dev))
+        ws = _cohort_ws.get(key)
+        if ws is None or ws.numel() < need:
+            ws = _cohort_ws.pop(key, None)   # free the old block before the larger one
+            del ws
+            ws = _cohort_ws[key] = torch.empty(max(need, 4), dtype=torch.uint8, device=dev)
+        _check(lib().spk_cosine_cohort_stats(x.data_ptr(), N, cohort.data_ptr(), Nc, E, int(k), mean.data_ptr(),
+                                             std.data_ptr(), ws.data_ptr(), need, _stream(dev)),
+               'spk_cosine_cohort_stats')
+    return mean, std
+
+
+def cohort_release_workspace():
+    """Drop the cached cohort-statistics workspaces (up to about 128 MiB per stream)."""
+    _cohort_ws.clear()
+
+
+def cosine_trials_norm(a: torch.Tensor, b: torch.Tensor, ia: torch.Tensor, ib: torch.Tensor, stats_a, stats_b):
+    """Normalised trial scores (spk_cosine_trials_norm): with s = cosine(a[ia[t]], b[ib[t]]), the
+    bits ``cosine_trials`` gives, and ``stats_a`` = (mean, std) over the rows of ``a``, ``stats_b``
+    over those of ``b`` (``cosine_cohort_stats``),
+    0.5 * ((s - mean_a) / max(std_a, 1e-6) + (s - mean_b) / max(std_b, 1e-6)) in float32."""
+    require_device_tensor(a, 'cosine_trials_norm')
+    dev = _dev_of(a)
+    a = a.to(torch.float32).contiguous()
+    b = b.to(device=dev, dtype=torch.float32).contiguous()
+    ia = ia.to(device=dev, dtype=torch.int64).contiguous()
+    ib = ib.to(device=dev, dtype=torch.int64).contiguous()
+    if ia.numel() != ib.numel():
+        raise HipError('cosine_trials_norm: ia and ib differ in length')
+    if ia.numel() and (int(ia.min()) < 0 or int(ia.max()) >= a.shape[0] or int(ib.min()) < 0
+                       or int(ib.max()) >= b.shape[0]):
+        raise HipError('cosine_trials_norm: trial index out of range')
+    st = []
+    for (m, s), n in ((stats_a, a.shape[0]), (stats_b, b.shape[0])):
+        m = torch.as_tensor(m).to(device=dev, dtype=torch.float32).contiguous()
+        s = torch.as_tensor(s).to(device=dev, dtype=torch.float32).contiguous()
+        if m.shape != (n,) or s.shape != (n,):
+            raise HipError('cosine_trials_norm: statistics must be (mean [rows], std [rows]) of each side')
+        st += [m, s]
+    out = torch.empty(ia.numel(), dtype=torch.float32, device=dev)
+    if ia.numel() == 0:
+        return out
+    with torch.cuda.device(dev):
+        _check(lib().spk_cosine_trials_norm(a.data_ptr(), b.data_ptr(), a.shape[1], ia.data_ptr(), ib.data_ptr(),
+                                            ia.numel(), st[0].data_ptr(), st[1].data_ptr(), st[2].data_ptr(),
+                                            st[3].data_ptr(), out.data_ptr(), _stream(dev)), 'spk_cosine_trials_norm')
+    return out

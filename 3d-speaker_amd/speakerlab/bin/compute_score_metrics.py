@@ -9,6 +9,12 @@ trial cosines are read out of row blocks of the enrol x test cosine affinity com
 the MFMA kernel (``spk_cosine_affinity``, sklearn ``cosine_similarity`` semantics: rows
 normalised, zero rows kept as zero) instead of one host cosine per trial line.  The
 metric arithmetic stays on the host (``speakerlab.utils.score_metrics``).
+
+MI355X build only: ``--score_norm {snorm,asnorm} --cohort_data DIR [--top_n N]`` normalise every
+trial score against a cohort of embeddings (``speakerlab.utils.score_norm``): the statistics of
+all enrol and all test embeddings against the cohort are computed once per run on the device
+(``spk_cosine_cohort_stats``), and ``<trial>.score`` and the metrics use the normalised scores
+(``spk_cosine_trials_norm``).  The default, ``none``, is the reference's raw cosine.
 """
 import argparse
 import os
@@ -34,6 +40,10 @@ parser.add_argument('--p_target', default=0.01, type=float, help='p_target in DC
 parser.add_argument('--c_miss', default=1, type=float, help='c_miss in DCF')
 parser.add_argument('--c_fa', default=1, type=float, help='c_fa in DCF')
 parser.add_argument('--no_plot', action='store_true', help='MI355X build: skip the EER curve PNG')
+parser.add_argument('--score_norm', default='none', choices=['none', 'snorm', 'asnorm'],
+                    help='MI355X build: cohort score normalisation (snorm: whole cohort, asnorm: its top_n best)')
+parser.add_argument('--cohort_data', default='', type=str, help='Cohort data dir (arks), needed by --score_norm')
+parser.add_argument('--top_n', default=300, type=int, help='Cohort scores kept per embedding by asnorm')
 
 LABELS = {'1': 1, 'target': 1, '0': 0, 'nontarget': 0}
 
@@ -64,9 +74,29 @@ def parse_trials(path):
     return pairs, np.array(labels)
 
 
-def trial_scores(enrol, test, pairs, device='cuda'):
+def parse_args(argv=None):
+    args = parser.parse_args(sys.argv[1:] if argv is None else argv)
+    if args.score_norm != 'none' and not args.cohort_data:
+        parser.error(f'--score_norm {args.score_norm} needs --cohort_data')
+    if args.score_norm == 'asnorm' and args.top_n < 1:
+        parser.error('--top_n must be at least 1')
+    return args
+
+
+def cohort_statistics(embs, cohort, top_n):
+    """{key: (mean, std)} of every embedding of ``embs`` against the cohort matrix (device)."""
+    from speakerlab.utils import score_norm
+    keys = sorted(embs)
+    mean, std = score_norm.cohort_stats(np.stack([np.asarray(embs[k], np.float32).reshape(-1) for k in keys]),
+                                        cohort, top_n)
+    return {k: (mean[i], std[i]) for i, k in enumerate(keys)}
+
+
+def trial_scores(enrol, test, pairs, device='cuda', stats=None):
     """Cosine score of every (enrol, test) trial, gathered on the GPU (``spk_cosine_trials``:
-    one wave per trial, O(trials x E) instead of the enrol x test affinity)."""
+    one wave per trial, O(trials x E) instead of the enrol x test affinity).  ``stats``: the
+    (enrol, test) ``cohort_statistics`` -- the scores are then normalised in the same gather
+    (``spk_cosine_trials_norm``)."""
     from speakerlab import _hip
     ekeys = sorted({p[0] for p in pairs})
     tkeys = sorted({p[1] for p in pairs})
@@ -76,7 +106,11 @@ def trial_scores(enrol, test, pairs, device='cuda'):
     tb = torch.from_numpy(np.stack([np.asarray(test[k], np.float32).reshape(-1) for k in tkeys])).to(device)
     rows = torch.tensor([eidx[p[0]] for p in pairs], dtype=torch.int64)
     cols = torch.tensor([tidx[p[1]] for p in pairs], dtype=torch.int64)
-    return _hip.cosine_trials(ea, tb, rows, cols).cpu().numpy()
+    if stats is None:
+        return _hip.cosine_trials(ea, tb, rows, cols).cpu().numpy()
+    se, st = ([torch.tensor(np.array([s[k][j] for k in keys], np.float32)) for j in (0, 1)]
+              for s, keys in ((stats[0], ekeys), (stats[1], tkeys)))
+    return _hip.cosine_trials_norm(ea, tb, rows, cols, se, st).cpu().numpy()
 
 
 def plot_eer_curves(fnr, fpr, scores, thres, labels, save_path):
@@ -116,17 +150,23 @@ def plot_eer_curves(fnr, fpr, scores, thres, labels, save_path):
 
 
 def main(argv=None):
-    args = parser.parse_args(sys.argv[1:] if argv is None else argv)
+    args = parse_args(argv)
     os.makedirs(args.scores_dir, exist_ok=True)
     logger = get_logger(fpath=os.path.join(args.scores_dir, 'result.metrics'), fmt='%(message)s')
     if not torch.cuda.is_available():
         raise RuntimeError('[ERROR]: no ROCm device: trial scoring runs on the GPU affinity kernel')
     enrol, test = collect(args.enrol_data), collect(args.test_data)
+    stats = None
+    if args.score_norm != 'none':
+        cohort = collect(args.cohort_data)
+        cohort = np.stack([np.asarray(cohort[k], np.float32).reshape(-1) for k in sorted(cohort)])
+        top_n = args.top_n if args.score_norm == 'asnorm' else None
+        stats = (cohort_statistics(enrol, cohort, top_n), cohort_statistics(test, cohort, top_n))
     results = {}
     for trial in args.trials:
         name = os.path.basename(trial)
         pairs, labels = parse_trials(trial)
-        scores = trial_scores(enrol, test, pairs)
+        scores = trial_scores(enrol, test, pairs, stats=stats)
         with open(os.path.join(args.scores_dir, f'{name}.score'), 'w') as f:
             f.writelines(' '.join(p) + ' %.5f\n' % s for p, s in zip(pairs, scores))
         fnr, fpr = compute_pmiss_pfa_rbst(scores, labels)

@@ -31,6 +31,9 @@
  *   spk_cosine_trials    the per-trial cosine_similarity loop of compute_score_metrics.py:102-118
  *   spk_ahc_average      AHCluster.__call__ after the affinity, speakerlab/process/cluster.py:139-156
  *                        (fastcluster linkage(method='average') + fcluster(criterion='distance'))
+ *   spk_topk_stats, spk_cosine_cohort_stats, spk_cosine_trials_norm
+ *                        nothing in the reference: the numpy partition / mean / std of cohort
+ *                        scores (S-norm / AS-norm) users write next to compute_score_metrics.py
  */
 #ifndef SPK_HIP_H
 #define SPK_HIP_H
@@ -280,6 +283,50 @@ int spk_ahc_workspace_bytes(int64_t N, size_t* bytes);
 int spk_ahc_average(const float* S, int64_t N, int64_t lds, float threshold, int32_t* labels, int32_t* n_clusters,
                     void* workspace, size_t workspace_bytes, void* stream);
 
+/* Cohort score normalisation of trial scores (S-norm, and AS-norm, its adaptive top-N form).  The
+ * reference has none; these entries replace what a user writes in numpy next to
+ * compute_score_metrics.py today, for the enrol side (and likewise the test side):
+ *     S = cosine_similarity(enrol, cohort)               # N x Nc, on the host
+ *     top = -np.partition(-S, K - 1, axis=1)[:, :K]      # the K best cohort scores of every row
+ *     mu, sd = top.mean(1), top.std(1)                   # ddof = 0
+ *     score[t] = 0.5 * ((s[t] - mu_e[ia[t]]) / sd_e[ia[t]] + (s[t] - mu_t[ib[t]]) / sd_t[ib[t]])
+ * K = Nc is S-norm.
+ *
+ * spk_topk_stats: mean[r] and std[r] (population, ddof = 0; device float32 [rows]) of the K largest
+ * of S[r][0 .. cols) for a device float32 matrix with row stride lds >= cols; only [0, cols) of a
+ * row is read.  The selection is exact: with v the K-th largest value of the row and g the number
+ * of entries strictly above it, sum = (sum of the entries above v) + (K - g) v, and the squares
+ * likewise, so equal values across the cut cannot change the result (-0.0 counts as +0.0).  Sums are
+ * fp64 in a fixed order without float atomics (the same input gives the same bits), var =
+ * max(sum2 / K - mean^2, 0).  K = 1 gives std 0.  Inputs are finite.
+ *
+ * spk_cosine_cohort_stats: the same statistics of the rows of the N x Nc cosine affinity of X
+ * [N, E] against the cohort C [Nc, E] (spk_cosine_affinity's kernel and semantics), without that
+ * matrix in memory at once: blocks of R rows are scored into the workspace and reduced in turn,
+ * R the largest multiple of 128 the workspace holds (R * Nc * 4 bytes, at least one block of 128).
+ * Rows are independent, so the result has the same bits for any workspace of at least min_bytes;
+ * spk_cosine_cohort_stats_workspace_bytes also returns the recommended size (blocks of about
+ * 128 MiB, which stay in the Infinity Cache between the passes of the selection).
+ *
+ * spk_cosine_trials_norm: spk_cosine_trials with the normalisation applied; s is the raw cosine of
+ * the same device function, bit for bit, and
+ *     scores[t] = 0.5f * ((s - mean_a[ia[t]]) / max(std_a[ia[t]], 1e-6f)
+ *                         + (s - mean_b[ib[t]]) / max(std_b[ib[t]], 1e-6f))
+ * in float32 (mean_a / std_a indexed like the rows of Ea, mean_b / std_b like those of Eb).  The
+ * 1e-6 floor keeps a degenerate cohort (all of the K best scores equal) finite.
+ *
+ * All four only enqueue.  Errors: a null pointer, rows / cols / N / Nc / n_trials < 1, lds < cols,
+ * K < 1, K > cols (K > Nc), E not a positive multiple of 4 SPK_E_INVALID; a workspace below
+ * min_bytes SPK_E_WORKSPACE; cols, N or Nc above 2^31 - 1, or a library built without the kernels,
+ * SPK_E_UNSUPPORTED.  Nothing is written on an error. */
+int spk_topk_stats(const float* S, int64_t rows, int64_t cols, int64_t lds, int32_t K, float* mean, float* std,
+                   void* stream);
+int spk_cosine_cohort_stats_workspace_bytes(int64_t N, int64_t Nc, size_t* min_bytes, size_t* bytes);
+int spk_cosine_cohort_stats(const float* X, int64_t N, const float* C, int64_t Nc, int32_t E, int32_t K, float* mean,
+                            float* std, void* workspace, size_t workspace_bytes, void* stream);
+int spk_cosine_trials_norm(const float* Ea, const float* Eb, int32_t E, const int64_t* ia, const int64_t* ib,
+                           int64_t n_trials, const float* mean_a, const float* std_a, const float* mean_b,
+                           const float* std_b, float* scores, void* stream);
 
 #ifdef __cplusplus
 }
