@@ -71,4 +71,35 @@ hipError_t launch_ahc_steps(int64_t N, float threshold, const AhcState& st, int 
 hipError_t launch_ahc_labels(int64_t N, const AhcState& st, int32_t* labels, int32_t* n_clusters, hipStream_t s)
     __attribute__((weak));
 
+// ---- batched form (ahc_batched.hip): one workgroup per problem runs the whole loop in one launch
+// largest N of a batched problem: the workgroup's state is 28 N bytes of LDS (112 KiB of the CU's
+// 160 KiB at the cap) and the working matrix 8 N^2 bytes of workspace (128 MiB)
+#define SPK_AHC_BATCH_MAX_N 4096
+// problems per launch: their descriptors travel as kernel arguments (40 bytes each)
+constexpr int kAhcBatchChunk = 64;
+
+struct AhcBatchProb {
+  const float* S;     // [N][lds] affinity
+  int32_t* labels;    // [N]
+  double* A;          // [N][N] working matrix, in the workspace
+  long long lds;
+  int N;
+  float thr;
+};
+
+struct AhcBatchArgs {
+  AhcBatchProb p[kAhcBatchChunk];
+  int32_t* n_clusters;   // [n], this chunk's slice
+  int n;
+};
+
+inline size_t ahc_batched_matrix_bytes(int64_t N) {
+  const size_t n = (size_t)N;
+  return (n * n * sizeof(double) + 255) / 256 * 256;
+}
+
+// two launches for a.n <= kAhcBatchChunk problems: A = double(upper triangle of S) mirrored for all
+// of them, then the loop and the labels, a workgroup per problem
+hipError_t launch_ahc_batched(const AhcBatchArgs& a, hipStream_t s) __attribute__((weak));
+
 }  // namespace spk

@@ -20,47 +20,13 @@
 //   repair  a workgroup per stale row rescans it over the active columns above it.
 // No kernel waits on another workgroup and every loop is bounded by N.
 #include "ahc.h"
+#include "ahc_dev.h"
 
 #include <algorithm>
 
 namespace spk {
 
 namespace {
-
-struct Cand {
-  double v;
-  int r, c;   // c < 0: no candidate
-};
-
-// b beats a: larger value, then smaller row, then smaller column
-__device__ __forceinline__ bool beats(const Cand& a, const Cand& b) {
-  if (b.c < 0) return false;
-  if (a.c < 0) return true;
-  if (b.v != a.v) return b.v > a.v;
-  if (b.r != a.r) return b.r < a.r;
-  return b.c < a.c;
-}
-
-// best candidate of the workgroup in thread 0: shuffles inside a wave, one LDS slot per wave
-template <int NT>
-__device__ __forceinline__ Cand block_best(Cand x, Cand* slots) {
-  constexpr int NW = NT / 64;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    Cand o;
-    o.v = __shfl_down(x.v, off);
-    o.r = __shfl_down(x.r, off);
-    o.c = __shfl_down(x.c, off);
-    if (beats(x, o)) x = o;
-  }
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (lane == 0) slots[w] = x;
-  __syncthreads();
-  if (threadIdx.x == 0)
-    for (int q = 1; q < NW; ++q)
-      if (beats(x, slots[q])) x = slots[q];
-  return x;
-}
 
 // A = double(S[min(r, c)][max(r, c)]): the upper triangle, which is what squareform() hands the
 // host linkage, mirrored so that the matrix is symmetric to the bit
@@ -131,14 +97,6 @@ __global__ void __launch_bounds__(ST) ahc_select_kernel(AhcState st, int N, doub
   st.ctrl[AHC_STEPS] += 1;
   st.size[i] = si + sj;
   st.active[j] = 0;
-}
-
-__device__ __forceinline__ double lance_williams(double a, double b, int si, int sj) {
-#pragma clang fp contract(off)
-  const double pa = (double)si * a;
-  const double pb = (double)sj * b;
-  const double num = pa + pb;
-  return num / (double)(si + sj);
 }
 
 __device__ __forceinline__ void mark_stale(const AhcState& st, int N, int k) {

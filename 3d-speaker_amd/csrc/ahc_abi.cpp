@@ -2,6 +2,8 @@
 // (ahc.h) and the chunked launch loop.  The host enqueues kAhcChunkSteps merge steps at a time
 // (never more than the N - 1 merges that can still happen) and reads the run word between
 // chunks; once select has cleared it, the rest of a chunk's launches return at their gate.
+// The batched entry (ahc_batched.hip) carves one working matrix per problem from the workspace and
+// hands kAhcBatchChunk problems to a launch; it never reads anything back.
 #include "ahc.h"
 #include "runtime.h"
 
@@ -19,6 +21,20 @@ int bad(int code, const std::string& msg) {
 int hip_fail(const char* what, hipError_t e) {
   set_error(std::string("spk_ahc_average: ") + what + ": " + hipGetErrorString(e));
   return e == hipErrorInvalidValue ? SPK_E_INVALID : SPK_E_HIP;
+}
+
+// SPK_OK, or the code of the first N[p] outside [1, SPK_AHC_BATCH_MAX_N] (spk_last_error set)
+int check_batched_sizes(const char* fn, const int64_t* N, int32_t n_prob) {
+  for (int32_t p = 0; p < n_prob; ++p) {
+    if (N[p] < 1)
+      return bad(SPK_E_INVALID, std::string(fn) + ": N[" + std::to_string(p) + "] = " + std::to_string((long long)N[p]) +
+                                    " is below 1");
+    if (N[p] > SPK_AHC_BATCH_MAX_N)
+      return bad(SPK_E_UNSUPPORTED, std::string(fn) + ": N[" + std::to_string(p) + "] = " +
+                                        std::to_string((long long)N[p]) + " is above the batched cap of " +
+                                        std::to_string(SPK_AHC_BATCH_MAX_N));
+  }
+  return SPK_OK;
 }
 
 }  // namespace
@@ -62,5 +78,58 @@ extern "C" int spk_ahc_average(const float* S, int64_t N, int64_t lds, float thr
     if (!run) break;
   }
   if (hipError_t e = launch_ahc_labels(N, st, labels, n_clusters, s)) return hip_fail("labels", e);
+  return SPK_OK;
+}
+
+extern "C" int spk_ahc_batched_max_n(void) { return SPK_AHC_BATCH_MAX_N; }
+
+extern "C" int spk_ahc_average_batched_workspace_bytes(const int64_t* N, int32_t n_prob, size_t* bytes) {
+  const char* fn = "spk_ahc_average_batched_workspace_bytes";
+  if (!bytes || n_prob < 0 || (n_prob > 0 && !N)) return bad(SPK_E_INVALID, std::string(fn) + ": invalid argument");
+  if (int rc = check_batched_sizes(fn, N, n_prob)) return rc;
+  size_t total = 0;
+  for (int32_t p = 0; p < n_prob; ++p) total += ahc_batched_matrix_bytes(N[p]);
+  *bytes = total;
+  return SPK_OK;
+}
+
+extern "C" int spk_ahc_average_batched(const float* const* S, const int64_t* N, const int64_t* lds,
+                                       const float* threshold, int32_t n_prob, int32_t* const* labels,
+                                       int32_t* n_clusters, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* fn = "spk_ahc_average_batched";
+  if (n_prob < 0) return bad(SPK_E_INVALID, std::string(fn) + ": n_prob < 0");
+  if (n_prob == 0) return SPK_OK;
+  if (!S || !N || !lds || !threshold || !labels || !n_clusters || !workspace)
+    return bad(SPK_E_INVALID, std::string(fn) + ": invalid argument (null pointer)");
+  if (int rc = check_batched_sizes(fn, N, n_prob)) return rc;
+  size_t need = 0;
+  for (int32_t p = 0; p < n_prob; ++p) {
+    if (!S[p] || !labels[p] || lds[p] < N[p])
+      return bad(SPK_E_INVALID, std::string(fn) + ": problem " + std::to_string(p) + ": null pointer or lds < N");
+    need += ahc_batched_matrix_bytes(N[p]);
+  }
+  if (workspace_bytes < need)
+    return bad(SPK_E_WORKSPACE, std::string(fn) + ": workspace of " + std::to_string(workspace_bytes) + " bytes, " +
+                                    std::to_string(need) + " needed");
+  if (reinterpret_cast<uintptr_t>(workspace) % alignof(double) != 0)
+    return bad(SPK_E_INVALID, std::string(fn) + ": the workspace must be 8-byte aligned");
+  if (!launch_ahc_batched) return bad(SPK_E_UNSUPPORTED, std::string(fn) + ": this build of the library has no kernels");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  char* at = reinterpret_cast<char*>(workspace);
+  for (int32_t lo = 0; lo < n_prob; lo += kAhcBatchChunk) {
+    AhcBatchArgs a;
+    a.n = (int)std::min<int32_t>(n_prob - lo, kAhcBatchChunk);
+    a.n_clusters = n_clusters + lo;
+    for (int q = 0; q < a.n; ++q) {
+      const int32_t p = lo + q;
+      a.p[q] = AhcBatchProb{S[p], labels[p], reinterpret_cast<double*>(at), (long long)lds[p], (int)N[p], threshold[p]};
+      at += ahc_batched_matrix_bytes(N[p]);
+    }
+    for (int q = a.n; q < kAhcBatchChunk; ++q) a.p[q] = AhcBatchProb{nullptr, nullptr, nullptr, 0, 0, 0.f};
+    if (hipError_t e = launch_ahc_batched(a, s)) {
+      set_error(std::string(fn) + ": launch: " + hipGetErrorString(e));
+      return e == hipErrorInvalidValue ? SPK_E_INVALID : SPK_E_HIP;
+    }
+  }
   return SPK_OK;
 }

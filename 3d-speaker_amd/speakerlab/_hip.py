@@ -104,6 +104,12 @@ SYMBOLS = {
     'spk_ahc_workspace_bytes': (ctypes.c_int, [ctypes.c_int64, ctypes.POINTER(ctypes.c_size_t)]),
     'spk_ahc_average': (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int64, ctypes.c_float, _P, _P, _P,
                                        ctypes.c_size_t, _P]),
+    'spk_ahc_batched_max_n': (ctypes.c_int, []),
+    'spk_ahc_average_batched_workspace_bytes': (ctypes.c_int, [ctypes.POINTER(ctypes.c_int64), ctypes.c_int32,
+                                                               ctypes.POINTER(ctypes.c_size_t)]),
+    'spk_ahc_average_batched': (ctypes.c_int, [ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_int64),
+                                               ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_float),
+                                               ctypes.c_int32, ctypes.POINTER(_P), _P, _P, ctypes.c_size_t, _P]),
     'spk_topk_stats': (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, _P, _P, _P]),
     'spk_cosine_cohort_stats_workspace_bytes': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64,
                                                                ctypes.POINTER(ctypes.c_size_t),
@@ -658,6 +664,55 @@ def ahc_average(S: torch.Tensor, threshold: float, return_count: bool = False):
         _check(lib().spk_ahc_average(S.data_ptr(), N, S.stride(0), float(threshold), labels.data_ptr(),
                                      count.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)), 'spk_ahc_average')
     return (labels, count) if return_count else labels
+
+
+def ahc_batched_max_n() -> int:
+    """Largest N of a problem ``ahc_average_batched`` takes (``SPK_AHC_BATCH_MAX_N``)."""
+    return int(lib().spk_ahc_batched_max_n())
+
+
+def ahc_average_batched(list_of_S, thresholds):
+    """``ahc_average`` of several affinities in one call (``spk_ahc_average_batched``: one workgroup
+    per problem, the whole merge loop in one launch).  ``list_of_S``: square device affinities on
+    one device, each N in [1, ``ahc_batched_max_n()``]; ``thresholds``: one float, or one per
+    problem.  Returns (labels, counts): a list of int32 [N_p] device tensors, each what
+    ``ahc_average`` gives for that problem alone, and the int32 [n] device cluster counts.  The
+    fp64 working matrices (8 N_p^2 bytes each) share the cached workspace of ``ahc_average``."""
+    mats = list(list_of_S)
+    n = len(mats)
+    thr = [float(thresholds)] * n if not hasattr(thresholds, '__len__') else [float(t) for t in thresholds]
+    if len(thr) != n:
+        raise HipError(f'ahc_average_batched: {n} affinities, {len(thr)} thresholds')
+    if n == 0:
+        return [], torch.zeros(0, dtype=torch.int32, device='cuda' if torch.cuda.is_available() else 'cpu')
+    for i, S in enumerate(mats):
+        require_device_tensor(S, 'ahc_average_batched')
+        if S.dim() != 2 or S.shape[0] != S.shape[1] or S.shape[0] < 1:
+            raise HipError(f'ahc_average_batched: expected square affinities, got {tuple(S.shape)}')
+        if S.device != mats[0].device:
+            raise HipError('ahc_average_batched: the affinities must be on one device')
+        if S.dtype != torch.float32 or S.stride(1) != 1 or S.stride(0) < S.shape[0]:
+            mats[i] = S.to(torch.float32).contiguous()
+    dev = _dev_of(mats[0])
+    sizes = (ctypes.c_int64 * n)(*[S.shape[0] for S in mats])
+    need = ctypes.c_size_t(0)
+    _check(lib().spk_ahc_average_batched_workspace_bytes(sizes, n, ctypes.byref(need)),
+           'spk_ahc_average_batched_workspace_bytes')
+    need = max(need.value, 8)
+    labels = [torch.empty(S.shape[0], dtype=torch.int32, device=dev) for S in mats]
+    counts = torch.empty(n, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        key = (dev.index, _stream(dev))
+        ws = _ahc_ws.get(key)
+        if ws is None or ws.numel() < need:
+            ws = _ahc_ws.pop(key, None)   # free the old block before the larger one
+            del ws
+            ws = _ahc_ws[key] = torch.empty(need, dtype=torch.uint8, device=dev)
+        _check(lib().spk_ahc_average_batched(
+            (_P * n)(*[S.data_ptr() for S in mats]), sizes, (ctypes.c_int64 * n)(*[S.stride(0) for S in mats]),
+            (ctypes.c_float * n)(*thr), n, (_P * n)(*[t.data_ptr() for t in labels]), counts.data_ptr(),
+            ws.data_ptr(), ws.numel(), _stream(dev)), 'spk_ahc_average_batched')
+    return labels, counts
 
 
 def ahc_release_workspace():

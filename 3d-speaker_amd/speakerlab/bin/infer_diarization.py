@@ -13,7 +13,8 @@ MI355X execution of the stages:
   sub-segment is circle-padded to the longest one by index arithmetic
   (``start + j mod len``), then GPU Fbank and the native ERes2NetV2 forward run on batches;
 * the N x N cosine affinity of the clustering runs on the GPU (MFMA), AHC / merging on the
-  host as in ``speakerlab.process.cluster`` (``--gpu_ahc``: the AHC loop on the GPU too).
+  host as in ``speakerlab.process.cluster`` (``--gpu_ahc``: the AHC loop on the GPU too;
+  ``--ahc_batch K``: one batched AHC launch for K files).
 
 Differences forced by the offline environment (documented in DESIGN.md):
 * TenVad (third-party binary library) is used when importable; otherwise an energy VAD
@@ -73,6 +74,9 @@ parser.add_argument('--gpu_resample', action='store_true',
 parser.add_argument('--gpu_ahc', action='store_true',
                     help='MI355X build: run the average-linkage AHC on the GPU as well (HIP kernels); the '
                          'N x N affinity is never copied to the host')
+parser.add_argument('--ahc_batch', default=1, type=int, metavar='K',
+                    help='MI355X build, with --gpu_ahc: cluster K files with one batched AHC launch (their '
+                         'affinities wait on the device); 1: every file on its own')
 parser.add_argument('--vad', choices=['auto', 'ten_vad', 'energy'], default='auto',
                     help='MI355X build: VAD engine (TenVad when importable, else the energy stand-in)')
 
@@ -216,6 +220,17 @@ class Diarization3Dspeaker:
                                                else float(vad_boundary_energy_percentile))
 
     def __call__(self, wav, wav_fs=None, speaker_num=None):
+        chunks, wav_data = self.do_front(wav, wav_fs)
+        if not chunks:
+            self.output_field_labels = []
+            return []
+        embeddings = self.do_emb_extraction(chunks, wav_data)
+        _, self.output_field_labels = self.do_clustering(chunks, embeddings, speaker_num)
+        return self.output_field_labels
+
+    def do_front(self, wav, wav_fs=None):
+        """Everything before the embeddings: audio, VAD and its post-processing (kept in the
+        ``last_vad_*`` fields), chunking.  Returns (chunks, wav_data)."""
         wav_data = load_audio(wav, wav_fs, self.fs, device=self.resample_device)
         flags, wav_vad = self.do_vad(wav_data)
         processed, refined, vad_time = self.postprocess_vad(flags, wav_vad)
@@ -229,12 +244,41 @@ class Diarization3Dspeaker:
             chunks = [[st, ed] for st, ed in vad_time]
         else:
             chunks = [c for st, ed in vad_time for c in self.chunk(st, ed)]
-        if not chunks:
-            self.output_field_labels = []
-            return []
-        embeddings = self.do_emb_extraction(chunks, wav_data)
-        _, self.output_field_labels = self.do_clustering(chunks, embeddings, speaker_num)
-        return self.output_field_labels
+        return chunks, wav_data
+
+    def defer(self, wav, wav_fs=None):
+        """``__call__`` up to the clustering, for ``--ahc_batch``: returns a job holding the chunks,
+        the embeddings, their cosine affinity (left on the device) and this file's ``last_vad_*``
+        fields; ``finish_deferred`` clusters a group of jobs with one batched call."""
+        from speakerlab import _hip
+        chunks, wav_data = self.do_front(wav, wav_fs)
+        job = {'chunks': chunks, 'embeddings': None, 'affinity': None,
+               'vad': {k: v for k, v in vars(self).items() if k.startswith('last_vad_')}}
+        if chunks:
+            job['embeddings'] = self.do_emb_extraction(chunks, wav_data)
+            X = torch.as_tensor(np.ascontiguousarray(job['embeddings'], dtype=np.float32)).to(self.device)
+            job['affinity'] = _hip.cosine_affinity(X)
+        return job
+
+    def finish_deferred(self, jobs, speaker_num=None):
+        """Cluster the jobs of ``defer`` with one ``from_affinities`` call; sets each job's
+        ``'segments'`` (what ``__call__`` returns for that file)."""
+        spk = speaker_num if speaker_num is not None else self.speaker_num
+        todo = [j for j in jobs if j['chunks']]
+        all_labels = self.cluster.from_affinities([j['embeddings'] for j in todo], [j['affinity'] for j in todo],
+                                                  speaker_num=spk)
+        for job in jobs:
+            job['segments'] = []
+        for job, labels in zip(todo, all_labels):
+            segs = [[c[0], c[1], int(k)] for c, k in zip(job['chunks'], labels)]
+            job['segments'] = vad_post.compressed_seg(segs)
+            job['affinity'] = None
+
+    def restore_deferred(self, job):
+        """Make ``job``'s file the current one again (``save_diar_output``, the side files)."""
+        for k, v in job['vad'].items():
+            setattr(self, k, v)
+        self.output_field_labels = job['segments']
 
     def do_vad(self, wav):
         return self.vad_model(wav[0])
@@ -439,12 +483,19 @@ def main_process(rank, nprocs, args, wav_list, port=None):
     if rank == 0 and not args.diable_progress_bar:
         from tqdm import tqdm
         mine = tqdm(mine, desc='Rank 0 processing')
-    for wav_path in mine:
+    pending = []   # --ahc_batch K > 1: (wav_path, job, seconds so far) of files not yet clustered
+
+    def flush():
         t0 = time.time()
-        diar(wav_path)
-        elapsed = time.time() - t0
-        if group is not None and rank != 0:
-            continue
+        diar.finish_deferred([job for _, job, _ in pending])
+        share = (time.time() - t0) / len(pending)
+        for wav_path, job, spent in pending:
+            t0 = time.time()
+            diar.restore_deferred(job)
+            write_outputs(wav_path, spent + share + time.time() - t0)
+        pending.clear()
+
+    def write_outputs(wav_path, elapsed):
         wav_id = os.path.basename(wav_path).rsplit('.', 1)[0]
         if args.out_dir is not None:
             out_file = os.path.join(args.out_dir, f'{wav_id}.{args.out_type}')
@@ -454,6 +505,21 @@ def main_process(rank, nprocs, args, wav_list, port=None):
         diar.group = None                         # the side files' pair pass is rank 0's alone
         write_side_files(diar, wav_path, out_file, wav_id, elapsed)
         diar.group = group
+
+    for wav_path in mine:
+        t0 = time.time()
+        if args.ahc_batch > 1:
+            pending.append((wav_path, diar.defer(wav_path), time.time() - t0))
+            if len(pending) == args.ahc_batch:
+                flush()
+            continue
+        diar(wav_path)
+        elapsed = time.time() - t0
+        if group is not None and rank != 0:
+            continue
+        write_outputs(wav_path, elapsed)
+    if pending:
+        flush()                                   # a trailing group smaller than K
     if group is not None:
         import torch.distributed as dist
         dist.barrier()
@@ -464,6 +530,12 @@ def main(argv=None):
     args = parser.parse_args(argv)
     if args.include_overlap and args.hf_access_token is None:
         parser.error('--hf_access_token is required when --include_overlap is specified.')
+    if args.ahc_batch < 1:
+        parser.error('--ahc_batch must be at least 1.')
+    if args.ahc_batch > 1 and not args.gpu_ahc:
+        parser.error('--ahc_batch needs --gpu_ahc: the batched AHC runs on the GPU.')
+    if args.ahc_batch > 1 and args.shard_chunks:
+        parser.error('--ahc_batch clusters whole files per rank and cannot be combined with --shard_chunks.')
     if args.wav.endswith('.wav'):
         wav_list = [args.wav]
     else:

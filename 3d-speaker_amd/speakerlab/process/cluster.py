@@ -80,6 +80,36 @@ def ahc_labels_gpu(S, fix_cos_thr: float) -> np.ndarray:
         return ahc_labels(S.cpu().numpy(), fix_cos_thr)
 
 
+def ahc_labels_gpu_batched(list_of_S, fix_cos_thr: float) -> list:
+    """``ahc_labels_gpu`` of several recordings' affinities with one batched call (csrc/
+    ahc_batched.hip: one workgroup per recording, the whole merge loop in one launch).  Returns one
+    label array per input, in the order of the inputs, each equal to ``ahc_labels_gpu`` of that
+    input.  An N above the batched cap goes through ``ahc_labels_gpu`` on its own."""
+    import torch
+    from speakerlab import _hip
+    mats = list(list_of_S)
+    if not mats:
+        return []
+    _require_device('device AHC')
+    cap = _hip.ahc_batched_max_n()
+    out = [None] * len(mats)
+    small = []
+    for idx, S in enumerate(mats):
+        if S.shape[0] > cap:
+            out[idx] = ahc_labels_gpu(S, fix_cos_thr)
+        elif S.shape[0] == 0:
+            out[idx] = np.zeros(0, dtype=np.int32)
+        else:
+            if not isinstance(S, torch.Tensor):
+                S = torch.from_numpy(np.ascontiguousarray(S, dtype=np.float32))
+            small.append((idx, S.cuda()))
+    if small:
+        labels, _ = _hip.ahc_average_batched([S for _, S in small], fix_cos_thr)
+        for (idx, _), lab in zip(small, labels):
+            out[idx] = lab.cpu().numpy()
+    return out
+
+
 def pruned_count(n: int, pval: float, min_pnum: int) -> int:
     """Entries zeroed per row by ``p_pruning`` (cluster.py:67-73): the reference slices
     ``argsort(row)[0:n_elems]`` with ``n_elems = min(int((1 - pval) * n), n - min_pnum)``, so a
@@ -238,6 +268,12 @@ class AHCluster:
             return ahc_labels_gpu(S, self.fix_cos_thr)
         return ahc_labels(S.cpu().numpy() if hasattr(S, 'cpu') else np.asarray(S), self.fix_cos_thr)
 
+    def from_affinities(self, list_of_S, **kwargs):
+        """``from_affinity`` of several recordings: one batched device call with ``device='gpu'``."""
+        if self.device == 'gpu':
+            return ahc_labels_gpu_batched(list_of_S, self.fix_cos_thr)
+        return [self.from_affinity(S) for S in list_of_S]
+
 
 class CommonClustering:
     """Dispatch (N < cluster_line -> AHC), then minor-cluster filtering and centroid merging."""
@@ -281,6 +317,32 @@ class CommonClustering:
         else:
             labels = self.cluster.from_affinity(S, **kwargs)
         return self._finish(labels, X)
+
+    def from_affinities(self, list_of_X, list_of_S, **kwargs):
+        """``from_affinity`` of several recordings, their AHC in one batched call where the back-end
+        has one (``AHCluster.from_affinities``): the same dispatch and post-processing per
+        recording, results in the order of the inputs."""
+        assert len(list_of_X) == len(list_of_S)
+        out = [None] * len(list_of_X)
+        short, full = [], []
+        for idx, (X, S) in enumerate(zip(list_of_X, list_of_S)):
+            assert len(X.shape) == 2 and S.shape[0] == S.shape[1] == X.shape[0]
+            if X.shape[0] <= 1:
+                out[idx] = np.zeros(X.shape[0], dtype=int)
+            elif X.shape[0] < self.cluster_line:
+                short.append(idx)
+            elif hasattr(self.cluster, 'from_affinities'):
+                full.append(idx)
+            else:
+                out[idx] = self.from_affinity(X, S, **kwargs)
+        groups = [(self.cluster_for_short, short), (self.cluster, full)]
+        if self.cluster_for_short is self.cluster:   # an AHC back-end: one call for both
+            groups = [(self.cluster, sorted(short + full))]
+        for back, todo in groups:
+            if todo:
+                for idx, labels in zip(todo, back.from_affinities([list_of_S[i] for i in todo])):
+                    out[idx] = self._finish(labels, list_of_X[idx])
+        return out
 
     def _finish(self, labels, X):
         labels = self.filter_minor_cluster(labels, X, self.min_cluster_size)

@@ -31,6 +31,7 @@
  *   spk_cosine_trials    the per-trial cosine_similarity loop of compute_score_metrics.py:102-118
  *   spk_ahc_average      AHCluster.__call__ after the affinity, speakerlab/process/cluster.py:139-156
  *                        (fastcluster linkage(method='average') + fcluster(criterion='distance'))
+ *   spk_ahc_average_batched  the same step for several recordings in one launch
  *   spk_topk_stats, spk_cosine_cohort_stats, spk_cosine_trials_norm
  *                        nothing in the reference: the numpy partition / mean / std of cohort
  *                        scores (S-norm / AS-norm) users write next to compute_score_metrics.py
@@ -282,6 +283,27 @@ int spk_symmetric_eig(float* A, int64_t N, int64_t lda, float* w, void* stream);
 int spk_ahc_workspace_bytes(int64_t N, size_t* bytes);
 int spk_ahc_average(const float* S, int64_t N, int64_t lds, float threshold, int32_t* labels, int32_t* n_clusters,
                     void* workspace, size_t workspace_bytes, void* stream);
+
+/* The same clustering for n_prob independent affinities in one call, for short and multi-file
+ * diarization: one workgroup per problem runs the whole merge loop inside a single launch, so the
+ * launch count (two per 64 problems) does not depend on N, and nothing is read back: no host
+ * synchronisation.  S, N, lds, threshold and labels are HOST arrays of n_prob entries; S[p]
+ * (device, N[p] x N[p], row stride lds[p] >= N[p], not modified) and labels[p] (device, N[p]) are
+ * device pointers, n_clusters is a device int32[n_prob].  Labels and counts of every problem are
+ * those spk_ahc_average gives for it alone, to the bit, whatever the order of the problems.
+ * Every N[p] must lie in [1, spk_ahc_batched_max_n()] (4096: the per-problem state lives in LDS);
+ * the workspace (device, 8-byte aligned) holds one fp64 matrix per problem,
+ * spk_ahc_average_batched_workspace_bytes (about 8 * sum N[p]^2).  n_prob == 0 succeeds and
+ * launches nothing.
+ * Errors, for the whole call and checked before anything is launched: a null pointer, n_prob < 0,
+ * N[p] < 1 or lds[p] < N[p] SPK_E_INVALID; N[p] above the cap SPK_E_UNSUPPORTED (cluster that
+ * problem with spk_ahc_average); a workspace too small SPK_E_WORKSPACE; a library built without
+ * the kernels SPK_E_UNSUPPORTED from spk_ahc_average_batched.  Nothing is written on an error. */
+int spk_ahc_batched_max_n(void);
+int spk_ahc_average_batched_workspace_bytes(const int64_t* N, int32_t n_prob, size_t* bytes);
+int spk_ahc_average_batched(const float* const* S, const int64_t* N, const int64_t* lds, const float* threshold,
+                            int32_t n_prob, int32_t* const* labels, int32_t* n_clusters, void* workspace,
+                            size_t workspace_bytes, void* stream);
 
 /* Cohort score normalisation of trial scores (S-norm, and AS-norm, its adaptive top-N form).  The
  * reference has none; these entries replace what a user writes in numpy next to
