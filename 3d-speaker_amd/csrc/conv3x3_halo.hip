@@ -22,6 +22,7 @@
 #include "common.h"
 #include "conv_epilogue.h"
 #include "conv_loader.h"
+#include "halo_whole_n.h"
 
 #ifndef SPK_EXP
 #define SPK_EXP 0
@@ -33,7 +34,27 @@
 #define SPK_HALO_PF2 0   // two halos in flight: measured neutral on ERes2NetV2, slower on ERes2Net-large / CAM++
 #endif
 
+#ifndef SPK_HALO_PROF
+#define SPK_HALO_PROF 0  // diagnostic build (tools/halo_prof.py): phase stamps of the 52-channel x3 forms
+#endif
+
 namespace spk {
+
+#if SPK_HALO_PROF
+// per-wave cycle counts of the lean 52-channel kernel's phases (tools/halo_prof.py), stored by
+// lane 0 of every wave (vector stores); the last launch stays
+constexpr int HP_PH = 8, HP_BLK = 512;
+__device__ long long halo_prof_buf[HP_BLK * 8 * HP_PH];
+#define HALO_PROF_BEGIN() long long tp_[HP_PH] = {0, 0, 0, 0, 0, 0, 0, 0}; long long tl_ = __builtin_amdgcn_s_memtime()
+#define HALO_STAMP(i) do { __builtin_amdgcn_sched_barrier(0); const long long now_ = __builtin_amdgcn_s_memtime(); \
+                           tp_[i] += now_ - tl_; tl_ = now_; __builtin_amdgcn_sched_barrier(0); } while (0)
+#define HALO_PROF_END(wave, lane) do { if ((lane) == 0 && blockIdx.x < HP_BLK) for (int i_ = 0; i_ < HP_PH; ++i_) \
+    halo_prof_buf[((size_t)blockIdx.x * 8 + (wave)) * HP_PH + i_] = tp_[i_]; } while (0)
+#else
+#define HALO_PROF_BEGIN() do {} while (0)
+#define HALO_STAMP(i) do {} while (0)
+#define HALO_PROF_END(wave, lane) do {} while (0)
+#endif
 
 namespace {
 
@@ -350,11 +371,12 @@ constexpr int halo_ks(int cin, int sh = 1) { return cin > 32 || sh == 2 ? 2 : 1;
 // (the frequency-strided form holds a 1.5x taller halo: one block per CU, so it takes the
 // second k-group too, for two waves per SIMD)
 
+// the sliced form (KS = 1, 2): the body of conv3x3_halo_x3_kernel below
 template <int CIN, int TW, bool ADD, int PIX, int KS, bool PLAIN, int SH>
-__global__ void __launch_bounds__(64 * (PIX / 32) * KS, 1)
-conv3x3_halo_x3_kernel(const ConvDesc d, int nsplit) {
+__device__ __forceinline__ void halo_x3_sliced(const ConvDesc& d, int nsplit) {
   SPK_GATE(d.run_if);
   using C = HaloX3Cfg<CIN, PIX, KS, SH>;
+  HALO_PROF_BEGIN();
   // scaled split (common.h): operand x 2^-s at staging, accumulators x 2^s after the taps
   const float sc = range_scale_flat(d.range_in), back = pow2_div(sc, 0), back_x = pow2_div(sc, -11);
   typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -485,9 +507,10 @@ conv3x3_halo_x3_kernel(const ConvDesc d, int nsplit) {
 #pragma unroll
   for (int q = 0; q < 2; ++q) {
     const int p = pw * 32 + 16 * q + (lane & 15);
-    abase16[q] = ((p / TW) * SH * HW + (p % TW)) * C::ROW + 8 * (lane >> 4) + 16 * C::KSG * kg;
+    abase16[q] = halo_pad::pix_off((p / TW) * SH * HW + (p % TW), lane, kg);
   }
-  const int bbase16 = (lane & 15) * C::ROW + 8 * (lane >> 4) + 16 * C::KSG * kg;
+  const int bbase16 = halo_pad::w_off(0, lane, kg, 0);
+  static_assert(!C::M16 || (C::ROW == halo_pad::ROW && C::NP == halo_pad::NP && C::KSG == 2), "halo_whole_n.h");
   // one tile; S = the register set this tile's successor-but-one is loaded into
   auto tile = [&](int t, auto setc) {
     constexpr int S = decltype(setc)::value;
@@ -566,7 +589,9 @@ conv3x3_halo_x3_kernel(const ConvDesc d, int nsplit) {
       }
       acc[0][0] = acc[0][0] * back + accx * back_x;
     }
+    HALO_STAMP(0);                                  // prefetch issue + taps
     __syncthreads();                                // halo reads done: the epilogue reuses it
+    HALO_STAMP(1);
     const int img = t / (ntx * nty), ty = (t / ntx) % nty, tx = t % ntx;
     const int y0 = ty * TH, x0 = tx * TW;
     if constexpr (KS > 1 && PLAIN) {
@@ -584,7 +609,9 @@ conv3x3_halo_x3_kernel(const ConvDesc d, int nsplit) {
         else
           slab[((r & 3) + 8 * (r >> 2) + 4 * lh) * SROW + li] = acc[0][0][r];
       }
+      HALO_STAMP(2);                                // partial sums -> LDS
       __syncthreads();
+      HALO_STAMP(3);
       const float* s0 = lds + pw * C::SLAB;
       const float* s1 = lds + (C::NW + pw) * C::SLAB;
       const int c4 = (lane & 7) * 4, n = n0 + c4, M = d.nimg * H * W;
@@ -649,9 +676,13 @@ conv3x3_halo_x3_kernel(const ConvDesc d, int nsplit) {
 #endif
       }
     }
+    HALO_STAMP(4);                                  // bias, activation, stores
     __syncthreads();                                // epilogue LDS reads done
+    HALO_STAMP(5);
     if (tn < ntiles) pf_store(std::integral_constant<int, NSET == 2 ? 1 - S : 0>{});
+    HALO_STAMP(6);                                  // wait for the next halo, split, stage
     __syncthreads();
+    HALO_STAMP(7);
   };
   if constexpr (NSET == 2) {
     for (; t < ntiles; t += 2 * tstride) {
@@ -660,6 +691,251 @@ conv3x3_halo_x3_kernel(const ConvDesc d, int nsplit) {
     }
   } else {
     for (; t < ntiles; t += tstride) tile(t, Set0{});
+  }
+  HALO_PROF_END(wave, lane);
+}
+
+// Whole-N form (KS = 3 of conv3x3_halo_x3_kernel): 52 -> 52 channels, stride 1, lean epilogue.
+// One block computes all 52 output channels of its tile from one staged halo, where the sliced
+// form stages every halo twice (once per 32-channel slice) and pads K to 64 and the second slice
+// to 32 channels.  The compact LDS layout (halo_whole_n.h: rows of 56 halves, 52 weight rows,
+// 154 KB in all) is what lets the whole N fit.
+//   - 8 waves = 4 pixel waves (32 pixels) x 2 channel halves (2 x 2 blocks of 16 each); a wave
+//     runs the full K of its quadrant (2 x 12 x 9 MFMAs), so no partial sums meet in LDS.
+//   - The MFMA takes the weights as A and the pixels as B: a lane then holds four consecutive
+//     channels of one pixel, and bias, activation and the 16-byte stores run straight from the
+//     accumulators.  No epilogue slab: the tile loop has two barriers (halo reads done; next
+//     halo staged) instead of four.
+//   - Staging is the sliced form's: unconditional buffer loads of the next tile's halo in
+//     flight during the taps, offsets materialised first, bias loaded once before them.
+// Persistent, one block per CU, tiles strided over the grid (any grid size gives the same bits).
+template <int TW, bool ADD>
+__device__ __forceinline__ void halo_x3_whole_n(const ConvDesc& d) {
+  SPK_GATE(d.run_if);
+  namespace L = halo_wn;
+  constexpr int PIX = 128, NT = 512, CIN = L::CIN, Q = CIN / 4, QP = L::ROW / 4;
+  // staging threads: a multiple of the quads per row, so a thread keeps one quad column
+  constexpr int NTS = NT / QP * QP, PSTEP = NTS / QP;
+  constexpr int TH = PIX / TW, HW = TW + 2, HH = TH + 2;
+  constexpr int PF = (HH * HW + PSTEP - 1) / PSTEP;               // staged float4 per thread
+  static_assert(HH * HW <= L::HALO_PIX, "halo buffer");
+  HALO_PROF_BEGIN();
+  const float sc = range_scale_flat(d.range_in), back = pow2_div(sc, 0), back_x = pow2_div(sc, -11);
+  typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+  typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+  typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
+  __shared__ __attribute__((aligned(16))) _Float16 lds[L::LDS_BYTES / 2];
+  _Float16* hh = lds;                               // halo hi / lo planes
+  _Float16* hlo = hh + L::HPLANE;
+  _Float16* wh = hlo + L::HPLANE;                   // weight hi / lo planes
+  _Float16* wl = wh + L::WPLANE;
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int H = d.Ho, W = d.Wo;
+  const int ntx = (W + TW - 1) / TW, nty = (H + TH - 1) / TH;
+  const int ntiles = d.nimg * ntx * nty;
+  const int tstride = gridDim.x;
+
+  // halo element r of this thread: quad qq of halo pixel tid / QP + PSTEP r (halo_x3_sliced)
+  const int qq = tid % QP, hp0 = tid / QP;
+  uint32_t hrc[PF];
+#pragma unroll
+  for (int r = 0; r < PF; ++r) {
+    const int p = hp0 + PSTEP * r;
+    hrc[r] = (tid < NTS && p < HH * HW && qq < Q) ? ((uint32_t)(p / HW) << 16) | (uint32_t)(p % HW) : 0x7FFF0000u;
+  }
+  const size_t img_px = (size_t)H * W;
+  f32x4 pa[PF], pb[ADD ? PF : 1];
+  auto pf_load = [&](int t) {
+    const int img = t / (ntx * nty), ty = (t / ntx) % nty, tx = t % ntx;
+    const int y0 = ty * TH - 1, x0 = tx * TW - 1;
+    const __amdgpu_buffer_rsrc_t r0 = make_rsrc(d.s0.p + img * img_px * d.s0.ld);
+    __amdgpu_buffer_rsrc_t r2;
+    if (ADD) r2 = make_rsrc(d.s0.p2 + img * img_px * d.s0.ld2);
+#pragma unroll
+    for (int r = 0; r < PF; ++r) {
+      const int gy = y0 + (int)(hrc[r] >> 16), gx = x0 + (int)(hrc[r] & 0xFFFFu);
+      const bool ok = ((unsigned)gy < (unsigned)H) & ((unsigned)gx < (unsigned)W);
+      const uint32_t pix = (uint32_t)(gy * W + gx);
+      // offsets in registers before the loads, the loads on every path (halo_x3_sliced)
+      uint32_t oa = ok ? (pix * (uint32_t)d.s0.ld + 4u * qq) * 4u : BUF_OOB;
+      asm volatile("" : "+v"(oa));
+      pa[r] = buf_load4(r0, oa);
+      if (ADD) {
+        uint32_t ob = ok ? (pix * (uint32_t)d.s0.ld2 + 4u * qq) * 4u : BUF_OOB;
+        asm volatile("" : "+v"(ob));
+        pb[r] = buf_load4(r2, ob);
+      }
+    }
+  };
+  auto pf_store = [&]() {
+    split_pass(sc, [&](auto split) {                // scaled split (common.h) when the word is set
+#pragma unroll
+      for (int r = 0; r < PF; ++r) {
+        const int p = hp0 + PSTEP * r;
+        if (tid < NTS && p < HH * HW) {             // quad 13 (channels 52..55) stores its zeros
+          f32x4 v = pa[r];
+          if (ADD) v += pb[r];
+          f16x4 h, l;
+          split(v, h, l);
+          *reinterpret_cast<f16x4*>(hh + p * L::ROW + 4 * qq) = h;
+          *reinterpret_cast<f16x4*>(hlo + p * L::ROW + 4 * qq) = l;
+        }
+      }
+    });
+  };
+
+  // this lane's operands: channel half ch, pixel wave pw; MFMA row 4 g + e of a weight block is
+  // channel 4 g + e, MFMA column j = lane & 15 of a pixel block is pixel lane_pixel(lane)
+  const int ch = wave & 1, pw = wave >> 1, g = lane >> 4;
+  // bias quads, loaded once, before the first halo prefetch (halo_x3_sliced)
+  f32x4 bias4[2];
+#pragma unroll
+  for (int cb = 0; cb < 2; ++cb) {
+    const int n = 32 * ch + 16 * cb + 4 * g;
+    bias4[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (d.bias && n < d.N) bias4[cb] = *reinterpret_cast<const f32x4*>(d.bias + n);
+  }
+  int t = blockIdx.x;
+  if (t < ntiles) pf_load(t);
+  // all nine taps of the split weights -> LDS, row position r holding channel wrow_channel(r)
+  for (int idx = tid; idx < 9 * L::WROWS * QP; idx += NT) {
+    const int q = idx % QP, r = (idx / QP) % L::WROWS, tap = idx / (QP * L::WROWS);
+    const int n = L::wrow_channel(r);
+    u16x4 h = {0, 0, 0, 0}, l = {0, 0, 0, 0};
+    if (n < CIN && n < d.N && q < Q) {
+      const size_t o = (size_t)n * d.Kp + tap * CIN + 4 * q;
+      h = *reinterpret_cast<const u16x4*>(d.wh + o);
+      l = *reinterpret_cast<const u16x4*>(d.wl + o);
+    }
+    *reinterpret_cast<u16x4*>(wh + tap * L::WTAP + r * L::ROW + 4 * q) = h;
+    *reinterpret_cast<u16x4*>(wl + tap * L::WTAP + r * L::ROW + 4 * q) = l;
+  }
+  if (tid < 9 * 2 * 4) {                            // each tap's two zero blocks, both planes
+    const int tap = tid >> 3, plane = (tid >> 2) & 1, z = tid & 3;
+    *reinterpret_cast<u16x4*>((plane ? wl : wh) + tap * L::WTAP + L::WROWS * L::ROW + 4 * z) = u16x4{0, 0, 0, 0};
+  }
+  if (t < ntiles) pf_store();
+  __syncthreads();
+
+  int pbase[2][2], wbase[2][2];                     // [block][32-deep step], halves
+#pragma unroll
+  for (int b = 0; b < 2; ++b)
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const int p = pw * 32 + 16 * b + L::lane_pixel(lane);
+      pbase[b][s] = L::pix_off((p / TW) * HW + (p % TW), lane, s);
+      wbase[b][s] = L::w_off(2 * ch + b, lane, s, 0);
+    }
+
+  for (; t < ntiles; t += tstride) {
+    const int tn = t + tstride;
+    if (tn < ntiles) pf_load(tn);                   // in flight during the taps and the epilogue
+    // [channel block][pixel block]: hi x hi, and the two cross terms
+    f32x4 a4[2][2], x4[2][2];
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {
+        a4[cb][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+        x4[cb][b] = a4[cb][b];
+      }
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap) {
+      const int toff = ((tap / 3) * HW + (tap % 3)) * L::ROW;
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        f16x8 xh[2], xl[2], vh[2], vl[2];
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+          xh[b] = *reinterpret_cast<const f16x8*>(hh + pbase[b][s] + toff);
+          xl[b] = *reinterpret_cast<const f16x8*>(hlo + pbase[b][s] + toff);
+          vh[b] = *reinterpret_cast<const f16x8*>(wh + wbase[b][s] + tap * L::WTAP);
+          vl[b] = *reinterpret_cast<const f16x8*>(wl + wbase[b][s] + tap * L::WTAP);
+        }
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+          for (int b = 0; b < 2; ++b) {
+            a4[cb][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vh[cb], xh[b], a4[cb][b], 0, 0, 0);
+            x4[cb][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vh[cb], xl[b], x4[cb][b], 0, 0, 0);
+            x4[cb][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vl[cb], xh[b], x4[cb][b], 0, 0, 0);
+          }
+      }
+    }
+    HALO_STAMP(0);                                  // prefetch issue + taps
+    // bias and activation on the accumulators, ahead of the barrier: it overlaps the other
+    // waves' taps
+    f32x4 o[2][2];
+    {
+      auto act_quads = [&](auto actc) {
+        constexpr int A = decltype(actc)::value;   // -1: general
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+          for (int b = 0; b < 2; ++b) {
+            o[cb][b] = a4[cb][b] * back + x4[cb][b] * back_x + bias4[cb];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              if constexpr (A >= 0) o[cb][b][e] = apply_act(o[cb][b][e], A);
+              else o[cb][b][e] = apply_act(apply_act(o[cb][b][e], d.act), d.act2);
+            }
+          }
+      };
+      if (d.act2 == ACT_NONE && d.act == ACT_HTANH) act_quads(std::integral_constant<int, ACT_HTANH>{});
+      else if (d.act2 == ACT_NONE && d.act == ACT_RELU) act_quads(std::integral_constant<int, ACT_RELU>{});
+      else act_quads(std::integral_constant<int, -1>{});
+    }
+    HALO_STAMP(4);                                  // bias, activation
+    __syncthreads();                                // every wave's halo reads done
+    HALO_STAMP(1);
+    if (tn < ntiles) pf_store();
+    HALO_STAMP(6);                                  // wait for the next halo, split, stage
+    // The stores come after the staging: its wait for the prefetched halo then finds only
+    // stores of the tile before in front of it, which completed during the taps.  Issued ahead
+    // of it they would be behind the halo loads in the queue (the memory counter retires in
+    // order), and the wait would take their write acknowledgements with it.
+    {
+      const int img = t / (ntx * nty), ty = (t / ntx) % nty, tx = t % ntx;
+      const int y0 = ty * TH, x0 = tx * TW, M = d.nimg * H * W;
+      int m[2];
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {
+        const int p = pw * 32 + 16 * b + L::lane_pixel(lane);
+        const int gy = y0 + p / TW, gx = x0 + p % TW;
+        m[b] = (gy < H && gx < W) ? (img * H + gy) * W + gx : -1;
+      }
+      float amax = 0.f;
+#pragma unroll
+      for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+          const int n = 32 * ch + 16 * cb + 4 * g;
+          if (n < d.N && m[b] >= 0 && m[b] < M) {
+            const f32x4 v = o[cb][b];
+            amax = fmaxf(amax, fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))));
+            *reinterpret_cast<f32x4*>(d.out + (size_t)m[b] * d.ldo + n) = v;
+          }
+        }
+      range_note(d.range_flag, amax);
+    }
+    HALO_STAMP(5);                                  // stores
+    __syncthreads();
+    HALO_STAMP(7);
+  }
+  HALO_PROF_END(wave, lane);
+}
+
+constexpr int halo_x3_threads(int pix, int ks) { return ks == 3 ? 512 : 64 * (pix / 32) * ks; }
+
+template <int CIN, int TW, bool ADD, int PIX, int KS, bool PLAIN, int SH>
+__global__ void __launch_bounds__(halo_x3_threads(PIX, KS), 1)
+conv3x3_halo_x3_kernel(const ConvDesc d, int nsplit) {
+  if constexpr (KS == 3) {
+    static_assert(CIN == halo_wn::CIN && PIX == 128 && PLAIN && SH == 1, "whole-N form");
+    halo_x3_whole_n<TW, ADD>(d);
+  } else {
+    halo_x3_sliced<CIN, TW, ADD, PIX, KS, PLAIN, SH>(d, nsplit);
   }
 }
 
@@ -683,6 +959,29 @@ hipError_t launch_halo_x3_k(const ConvDesc& d, int nsplit, int tiles, hipStream_
   return hipGetLastError();
 }
 
+// SPK_HALO_WHOLE_N=0: the 52 -> 52 lean convs back on the sliced form (the A/B arm).  Read at
+// every call, as is the grid cap below, so that one process can compare both settings.
+bool halo_whole_n_on() {
+  const char* e = std::getenv("SPK_HALO_WHOLE_N");
+  return !(e && *e && std::atoi(e) == 0);
+}
+
+// the whole-N form: 52 -> 52 channels, stride 1, lean epilogue
+bool halo_whole_n_ok(const ConvDesc& d, bool plain) {
+  return plain && d.s0.cin == halo_wn::CIN && d.N == halo_wn::CIN && d.s0.sh == 1 && halo_whole_n_on();
+}
+
+template <int TW, bool ADD>
+hipError_t launch_halo_whole_n(const ConvDesc& d, int tiles, hipStream_t s) {
+  auto k = conv3x3_halo_x3_kernel<halo_wn::CIN, TW, ADD, 128, 3, true, 1>;
+  int g = std::min(tiles, device_cus());            // persistent: one block per CU (LDS)
+  // SPK_HALO_GRID_CAP=n (tests): at most n blocks; the result does not depend on the grid
+  if (const char* e = std::getenv("SPK_HALO_GRID_CAP"))
+    if (std::atoi(e) > 0) g = std::min(g, std::atoi(e));
+  hipLaunchKernelGGL(k, dim3(g), dim3(512), 0, s, d, 1);
+  return hipGetLastError();
+}
+
 // PLAIN: no residual / post-affine / ragged mask, so the epilogue issues no load behind
 // the next tile's halo prefetch (conv_epilogue.h); the common case (every Res2Net 3x3)
 template <int CIN, int TW, int PIX>
@@ -696,6 +995,10 @@ hipError_t launch_halo_x3_tw(const ConvDesc& d, hipStream_t s) {
     if (d.s0.sh == 2)
       return plain ? launch_halo_x3_k<CIN, TW, PIX, false, true, 2>(d, nsplit, tiles, s)
                    : launch_halo_x3_k<CIN, TW, PIX, false, false, 2>(d, nsplit, tiles, s);
+  }
+  if constexpr (CIN == halo_wn::CIN && PIX == 128) {
+    if (halo_whole_n_ok(d, plain))
+      return d.s0.p2 ? launch_halo_whole_n<TW, true>(d, tiles, s) : launch_halo_whole_n<TW, false>(d, tiles, s);
   }
   if (d.s0.p2)
     return plain ? launch_halo_x3_k<CIN, TW, PIX, true, true>(d, nsplit, tiles, s)
@@ -814,11 +1117,12 @@ std::string halo_kernel_name(const ConvDesc& d) {
   const bool add = d.s0.p2 != nullptr || d.s0.ld2 > 0;
   if (x3_halo_ok(d)) {
     const int px = 128;
+    const bool plain = !d.res && d.ldr == 0 && !d.post_scale && !d.rowlen && !d.osplit &&
+                       ((double)d.nimg * d.Ho * d.Wo * d.ldo + d.N) * 4.0 < 0x7FFFFFF0;
+    const int ks = halo_whole_n_ok(d, plain) ? 3 : halo_ks(d.s0.cin, d.s0.sh);   // 3: the whole-N form
     return "conv3x3_halo_x3_kernel<" + std::to_string(d.s0.cin) + ", " + std::to_string(pick_tw(d.Ho, d.Wo, px)) +
-           ", " + (add ? "true" : "false") + ", " + std::to_string(px) + ", " + std::to_string(halo_ks(d.s0.cin, d.s0.sh)) + ", " +
-           ((!d.res && d.ldr == 0 && !d.post_scale && !d.rowlen && !d.osplit &&
-             ((double)d.nimg * d.Ho * d.Wo * d.ldo + d.N) * 4.0 < 0x7FFFFFF0) ? "true" : "false") + ", " +
-           std::to_string(d.s0.sh) + ">";
+           ", " + (add ? "true" : "false") + ", " + std::to_string(px) + ", " + std::to_string(ks) + ", " +
+           (plain ? "true" : "false") + ", " + std::to_string(d.s0.sh) + ">";
   }
   if (persistent_ok(d))
     return "conv3x3_halo_persistent_kernel<" + std::to_string(d.s0.cin) + ", " + std::to_string(tw) + ", " +
@@ -854,3 +1158,11 @@ hipError_t launch_conv3x3_halo(const ConvDesc& d, hipStream_t s) {
 }
 
 }  // namespace spk
+
+#if SPK_HALO_PROF
+extern "C" int spk_exp_halo_prof(long long* host, size_t n) {
+  const size_t all = sizeof(spk::halo_prof_buf) / sizeof(long long);
+  return hipMemcpyFromSymbol(host, HIP_SYMBOL(spk::halo_prof_buf), std::min(n, all) * sizeof(long long), 0,
+                             hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
+}
+#endif
