@@ -116,17 +116,21 @@ def _run(group, cluster_type):
     return emb, spk, segs
 
 
-def _patch():
-    # host stand-ins of the GPU kernels the clustering would call
+def _patch(setattr_=setattr):
+    """Host stand-ins of the GPU kernels the clustering would call.  In the pytest process they go
+    in through ``monkeypatch.setattr`` and come out again with the test: left in place they would
+    stand in for ``_hip.cosine_affinity`` and the spectral entry points in every GPU test that
+    runs later in the same process.  A spawned worker patches its own process for good."""
     import speakerlab._hip as hip
-    hip.cosine_affinity = lambda a, b=None, out=None: _host_affinity(a, b)
-    cl.cosine_affinity = lambda X: _host_affinity(torch.as_tensor(np.asarray(X, np.float32))).numpy()
+    setattr_(hip, 'cosine_affinity', lambda a, b=None, out=None: _host_affinity(a, b))
+    setattr_(cl, 'cosine_affinity', lambda X: _host_affinity(torch.as_tensor(np.asarray(X, np.float32))).numpy())
 
     def spec_aff(S, mn=1, mx=10, pval=0.02, min_pnum=6, oracle_num=None):
         return cl.spectral_labels(np.asarray(S.cpu() if hasattr(S, 'cpu') else S, np.float64), mn, mx, pval,
                                   min_pnum, oracle_num)
-    cl.spectral_labels_gpu_affinity = spec_aff
-    cl.spectral_labels_gpu = lambda X, *a: spec_aff(_host_affinity(torch.as_tensor(np.asarray(X, np.float32))), *a)
+    setattr_(cl, 'spectral_labels_gpu_affinity', spec_aff)
+    setattr_(cl, 'spectral_labels_gpu',
+             lambda X, *a: spec_aff(_host_affinity(torch.as_tensor(np.asarray(X, np.float32))), *a))
 
 
 def _worker(rank, world, port, cluster_type, q):
@@ -141,8 +145,8 @@ def _worker(rank, world, port, cluster_type, q):
 
 
 @pytest.mark.parametrize('cluster_type', ['AHC', 'spectral'])
-def test_shard_chunks_two_ranks_equals_one_process(cluster_type):
-    _patch()
+def test_shard_chunks_two_ranks_equals_one_process(cluster_type, monkeypatch):
+    _patch(monkeypatch.setattr)
     emb1, spk1, segs1 = _run(None, cluster_type)
     assert spk1 >= 2, 'the synthetic meeting should separate into several speakers'
     ctx = mp.get_context('spawn')

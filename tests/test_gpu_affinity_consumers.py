@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+from data_ref import np_topk
 from speakerlab import _hip
 
 pytestmark = pytest.mark.gpu
@@ -18,16 +19,6 @@ def np_cos(a, b):
         n[n == 0] = 1.0
         return x / n
     return nrm(a) @ nrm(b).T
-
-
-def np_topk(S, k, self_off):
-    S = S.copy()
-    if self_off is not None:
-        r = np.arange(S.shape[0])
-        ok = r + self_off < S.shape[1]
-        S[r[ok], r[ok] + self_off] = -np.inf
-    order = np.lexsort((np.broadcast_to(np.arange(S.shape[1]), S.shape), -S), axis=1)[:, :k]
-    return np.take_along_axis(S, order, 1), order
 
 
 @pytest.mark.parametrize('na,nb,e,k,self_off', [(300, 1000, 192, 1, 0), (129, 5000, 192, 8, 100), (1, 7, 512, 5, None),

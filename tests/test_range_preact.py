@@ -97,6 +97,12 @@ def test_hot_preactivation_matches_fp64(factor):
         out = m(feats.to(dev)).cpu().numpy()
     h = m._hip_handle(dev)
     assert not h.last_forward_exact
+    # the forward under test is the scaled fp16x3 GEMM: the plan routes the amplifying layer to it,
+    # and the handle has no exact-fp32 twin to fall back on
+    B, T = feats.shape[:2]
+    kern = {name: k for name, k, _ in h.plan(B, T)}
+    assert kern['xvector.block1.tdnnd1.linear1'].startswith('conv_gemm_x3_kernel'), kern['xvector.block1.tdnnd1.linear1']
+    assert h.guard_plan(B, T)['twin_segments'] == 0
     assert np.isfinite(out).all()
     err = helpers.rel_err(out, ref).max()
     assert err < tol, (err, tol)
