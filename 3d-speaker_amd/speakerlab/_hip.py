@@ -66,6 +66,10 @@ SYMBOLS = {
                                          ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), _P,
                                          ctypes.c_size_t]),
     'spk_resample_f32': (ctypes.c_int, [_P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P]),
+    'spk_vad_energy_sizes': (ctypes.c_int, [ctypes.c_int64, ctypes.POINTER(ctypes.c_int64),
+                                            ctypes.POINTER(ctypes.c_int64)]),
+    'spk_vad_energy_f32': (ctypes.c_int, [_P, _P, ctypes.c_int32, _P, _P, _P, _P, _P]),
+    'spk_vad_apply_intervals_f32': (ctypes.c_int, [_P, ctypes.c_int64, _P, _P, ctypes.c_int64, _P, _P]),
     'spk_model_create': (ctypes.c_int, [ctypes.POINTER(spk_model_config_t), ctypes.POINTER(spk_weight_t),
                                         ctypes.c_int32, ctypes.POINTER(_P)]),
     'spk_model_destroy': (ctypes.c_int, [_P]),
@@ -298,6 +302,84 @@ def resample(wavs, orig_freq: int, new_freq: int, lengths=None):
         return [out[out_off[i]:out_off[i + 1]] for i in range(B)]
     out = out.view(B, -1) if B else out.view(0, 0)
     return out[0] if squeeze else out
+
+
+# ----------------------------------------------------------------------------- VAD front end
+def vad_energy_sizes(n_samples: int):
+    """(n16, n20) of ``vad_energy`` for ``n_samples`` at 16 kHz: 16 ms frames and 20 ms / 10 ms
+    windows (no GPU needed)."""
+    n16, n20 = ctypes.c_int64(), ctypes.c_int64()
+    _check(lib().spk_vad_energy_sizes(int(n_samples), ctypes.byref(n16), ctypes.byref(n20)), 'spk_vad_energy_sizes')
+    return n16.value, n20.value
+
+
+def vad_energy(wav):
+    """The two mean-square tracks of the VAD front end (spk_vad_energy_f32), samples clipped to
+    [-1, 1] first, 16 kHz: ``e16`` float64 [L // 256] (the 16 ms frames of the energy VAD) and
+    ``e20`` float32 [(L - 320) // 160 + 1] (the 20 ms / 10 ms windows of ``vad_post.frame_energy``).
+
+    ``wav``: a 1-D float32 device tensor -> (e16, e20) device tensors; a list of 1-D device tensors
+    is a ragged batch in one launch -> a list of (e16, e20) pairs of views into two buffers, each
+    with the bits it has when run alone.  Non-finite samples are outside the contract."""
+    as_list = isinstance(wav, (list, tuple))
+    wavs = list(wav) if as_list else [wav]
+    if not wavs:
+        return []
+    for w in wavs:
+        require_device_tensor(w, 'vad_energy')
+        if w.dim() != 1:
+            raise HipError(f'vad_energy: expected 1-D signals, got {tuple(w.shape)}')
+    dev = _dev_of(wavs[0])
+    if len(wavs) == 1:
+        flat = wavs[0].to(torch.float32).contiguous()
+    else:
+        flat = torch.cat([w.to(torch.float32) for w in wavs])
+    off = [[0], [0], [0]]
+    for w in wavs:
+        for o, n in zip(off, (int(w.numel()),) + vad_energy_sizes(int(w.numel()))):
+            o.append(o[-1] + n)
+    offs = torch.tensor(off, dtype=torch.int64).to(dev, non_blocking=True)
+    e16 = torch.empty(max(off[1][-1], 1), dtype=torch.float64, device=dev)
+    e20 = torch.empty(max(off[2][-1], 1), dtype=torch.float32, device=dev)
+    if flat.numel() == 0:
+        flat = torch.zeros(1, dtype=torch.float32, device=dev)   # no utterance has a sample: nothing is read
+    with torch.cuda.device(dev):
+        _check(lib().spk_vad_energy_f32(flat.data_ptr(), offs[0].data_ptr(), len(wavs), e16.data_ptr(),
+                                        offs[1].data_ptr(), e20.data_ptr(), offs[2].data_ptr(), _stream(dev)),
+               'spk_vad_energy_f32')
+    res = [(e16[off[1][i]:off[1][i + 1]], e20[off[2][i]:off[2][i + 1]]) for i in range(len(wavs))]
+    return res if as_list else res[0]
+
+
+def vad_apply_intervals(wav: torch.Tensor, starts, ends) -> torch.Tensor:
+    """``wav`` (1-D float32 device tensor) with every sample outside the intervals
+    [starts[k], ends[k]) zeroed (spk_vad_apply_intervals_f32): ``vad_post.apply_mask`` for the mask
+    whose runs are the intervals.  ``starts`` / ``ends``: sorted, disjoint sample indices in
+    [0, len(wav)] (sequences or int64 tensors); none gives zeros."""
+    require_device_tensor(wav, 'vad_apply_intervals')
+    if wav.dim() != 1:
+        raise HipError(f'vad_apply_intervals: expected a 1-D signal, got {tuple(wav.shape)}')
+    dev = _dev_of(wav)
+    wav = wav.to(torch.float32).contiguous()
+    L = int(wav.numel())
+    s = torch.as_tensor(starts, dtype=torch.int64).reshape(-1)
+    e = torch.as_tensor(ends, dtype=torch.int64).reshape(-1)
+    n = int(s.numel())
+    if int(e.numel()) != n:
+        raise HipError('vad_apply_intervals: starts and ends differ in length')
+    if n:
+        sh, eh = s.cpu(), e.cpu()
+        if (int(sh[0]) < 0 or int(eh[-1]) > L or bool((eh <= sh).any()) or bool((sh[1:] < eh[:-1]).any())):
+            raise HipError('vad_apply_intervals: intervals must be non-empty, sorted, disjoint and within the signal')
+    iv = torch.stack([s, e]).to(dev, non_blocking=True) if n else None
+    out = torch.empty_like(wav)
+    if L == 0:
+        return out
+    with torch.cuda.device(dev):
+        _check(lib().spk_vad_apply_intervals_f32(wav.data_ptr(), L, iv[0].data_ptr() if n else None,
+                                                 iv[1].data_ptr() if n else None, n, out.data_ptr(), _stream(dev)),
+               'spk_vad_apply_intervals_f32')
+    return out
 
 
 # ----------------------------------------------------------------------------- models

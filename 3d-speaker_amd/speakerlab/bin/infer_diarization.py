@@ -8,7 +8,9 @@ outputs (RTTM or JSON, plus the ``.vad_info.json`` / ``.meta.json`` / ``.pairs.j
 MI355X execution of the stages:
 
 * VAD post-processing, boundary refinement, interval and sub-segment bookkeeping run as
-  vectorised numpy (``speakerlab.utils.vad_post``) — bit-identical to the reference loops;
+  vectorised numpy (``speakerlab.utils.vad_post``) — bit-identical to the reference loops
+  (``--gpu_vad``: the frame energies and the masked audio come from HIP kernels, the signal is
+  uploaded once, and the same decisions are taken from run lengths instead of per-sample arrays);
 * sub-segment extraction is a gather on the device: the whole wav is uploaded once, every
   sub-segment is circle-padded to the longest one by index arithmetic
   (``start + j mod len``), then GPU Fbank and the native ERes2NetV2 forward run on batches;
@@ -77,6 +79,10 @@ parser.add_argument('--gpu_ahc', action='store_true',
 parser.add_argument('--ahc_batch', default=1, type=int, metavar='K',
                     help='MI355X build, with --gpu_ahc: cluster K files with one batched AHC launch (their '
                          'affinities wait on the device); 1: every file on its own')
+parser.add_argument('--gpu_vad', action='store_true',
+                    help='MI355X build: compute the VAD front end\'s frame energies and the masked audio on the '
+                         'GPU (HIP kernels) and refine the boundaries from run lengths; the signal is uploaded '
+                         'once and no per-sample array is built on the host')
 parser.add_argument('--vad', choices=['auto', 'ten_vad', 'energy'], default='auto',
                     help='MI355X build: VAD engine (TenVad when importable, else the energy stand-in)')
 
@@ -128,18 +134,32 @@ class EnergyVad:
         self.hop_size = int(frame_ms * sample_rate / 1000)
         self.range_db, self.floor_db = range_db, floor_db
 
-    def __call__(self, wav_1d):
+    @staticmethod
+    def _clipped(wav_1d):
         x = wav_1d.detach().cpu().numpy() if hasattr(wav_1d, 'detach') else np.asarray(wav_1d)
-        x = np.clip(x.astype(np.float32), -1.0, 1.0)
-        if x.size == 0:
-            return [], x
+        return np.clip(x.astype(np.float32), -1.0, 1.0)
+
+    def _mean_square(self, x):
         n = len(x) // self.hop_size
-        if n == 0:
-            return [], x
         fr = x[:n * self.hop_size].reshape(n, self.hop_size).astype(np.float64)
-        db = 10 * np.log10(np.mean(fr ** 2, axis=1) + 1e-12)
+        return np.mean(fr ** 2, axis=1)
+
+    def frame_energy(self, wav_1d):
+        """fp64 mean square of every whole 16 ms frame of the clipped signal, [len // hop]
+        (``_hip.vad_energy`` computes the same track on the device)."""
+        return self._mean_square(self._clipped(wav_1d))
+
+    def flags_from_energy(self, e16):
+        """0/1 flags from the frame energies: the decision rule of the class."""
+        if len(e16) == 0:
+            return []
+        db = 10 * np.log10(np.asarray(e16, dtype=np.float64) + 1e-12)
         flags = (db > max(np.percentile(db, 95) - self.range_db, self.floor_db)).astype(np.int64)
-        return flags.tolist(), x
+        return flags.tolist()
+
+    def __call__(self, wav_1d):
+        x = self._clipped(wav_1d)
+        return self.flags_from_energy(self._mean_square(x)), x
 
 
 def get_voice_activity_detection_model(device=None, cache_dir=None, threshold=0.5, engine='auto'):
@@ -169,6 +189,24 @@ def get_voice_activity_detection_model(device=None, cache_dir=None, threshold=0.
     return EnergyVad()
 
 
+def _lazy_vad_field(name):
+    """A ``last_vad_*`` field that may hold a thunk (``gpu_vad``: the per-sample arrays are built on
+    first access only).  The value lives in ``last_vad_<name>_value``, a ``last_vad_*`` entry of the
+    instance like the plain fields, so ``defer`` / ``restore_deferred`` carry it along."""
+    key = f'last_vad_{name}_value'
+
+    def get(self):
+        v = self.__dict__.get(key)
+        if callable(v):
+            v = self.__dict__[key] = v()
+        return v
+
+    def put(self, v):
+        self.__dict__[key] = v
+
+    return property(get, put)
+
+
 class Diarization3Dspeaker:
     """VAD -> sub-segments -> GPU embeddings -> clustering -> merged segments.
 
@@ -176,12 +214,16 @@ class Diarization3Dspeaker:
     ``save_diar_output(out_file, wav_id)`` writes RTTM or JSON (reference :203-330, :727-755).
     """
 
+    last_vad_masked_audio = _lazy_vad_field('masked_audio')
+    last_vad_processed_mask = _lazy_vad_field('processed_mask')
+    last_vad_refined_mask = _lazy_vad_field('refined_mask')
+
     def __init__(self, device=None, include_overlap=False, hf_access_token=None, speaker_num=None,
                  model_cache_dir=None, no_chunk_after_vad=False, vad_min_speech_ms=None, vad_max_silence_ms=None,
                  vad_energy_threshold=None, vad_boundary_expansion_ms=None, vad_boundary_energy_percentile=None,
                  vad_threshold=0.5, cluster_mer_cos=0.3, cluster_fix_cos_thr=0.3, cluster_min_cluster_size=0,
                  chunk_dur=1.5, chunk_step=0.75, batch_size=64, synthetic_weights=False, vad='auto', group=None,
-                 gpu_resample=False, gpu_ahc=False):
+                 gpu_resample=False, gpu_ahc=False, gpu_vad=False):
         if include_overlap and hf_access_token is None:
             raise ValueError('hf_access_token is required when include_overlap is True.')
         if include_overlap:
@@ -208,6 +250,9 @@ class Diarization3Dspeaker:
         # audio at another rate than self.fs: resampled by the HIP kernel on self.device instead
         # of the host conv1d (fileio.load_audio(device=...)); same [1, L] CPU tensor either way
         self.resample_device = self.device if gpu_resample and self.device.type == 'cuda' else None
+        # the per-sample arithmetic of the VAD front (frame energies, masked copy) on self.device
+        # (HIP kernels), the decisions at run-length granularity on the host: do_front_gpu
+        self.gpu_vad = bool(gpu_vad)
         self.output_field_labels = None
         self.last_vad_time = self.last_vad_time_raw = self.last_vad_time_processed = None
         self.last_vad_masked_audio = self.last_vad_refined_mask = self.last_vad_processed_mask = None
@@ -231,6 +276,8 @@ class Diarization3Dspeaker:
     def do_front(self, wav, wav_fs=None):
         """Everything before the embeddings: audio, VAD and its post-processing (kept in the
         ``last_vad_*`` fields), chunking.  Returns (chunks, wav_data)."""
+        if self.gpu_vad:
+            return self.do_front_gpu(wav, wav_fs)
         wav_data = load_audio(wav, wav_fs, self.fs, device=self.resample_device)
         flags, wav_vad = self.do_vad(wav_data)
         processed, refined, vad_time = self.postprocess_vad(flags, wav_vad)
@@ -246,6 +293,53 @@ class Diarization3Dspeaker:
             chunks = [c for st, ed in vad_time for c in self.chunk(st, ed)]
         return chunks, wav_data
 
+    def do_front_gpu(self, wav, wav_fs=None):
+        """``do_front`` with ``gpu_vad``: the signal is uploaded once (or stays where the GPU
+        resampler left it) and is the ``wav_data`` returned, which ``do_emb_extraction`` reads in
+        place; one ``_hip.vad_energy`` launch gives the two energy tracks, and only those come back
+        (about 3 MB for an hour).  Every ``last_vad_*`` field holds what ``do_front`` puts there;
+        the masks and the masked audio are built when first read."""
+        wav_data = load_audio(wav, wav_fs, self.fs, device=self.resample_device, keep_on_device=True)
+        flags, e20, dev_wav = self.front_energies(wav_data)
+        return self.front_decisions(flags, e20, dev_wav), dev_wav[None]
+
+    def front_energies(self, wav_data):
+        """(VAD flags, 20 ms / 10 ms energies of the boundary refinement, the [L] device signal)."""
+        from speakerlab import _hip
+        if self.fs != 16000:
+            raise ValueError('gpu_vad: the energy kernel is written for 16 kHz audio')
+        x = wav_data[0] if wav_data.dim() == 2 else wav_data
+        dev_wav = x.to(self.device, torch.float32).contiguous()
+        e16, e20 = _hip.vad_energy(dev_wav)
+        if hasattr(self.vad_model, 'flags_from_energy'):
+            flags = self.vad_model.flags_from_energy(e16.cpu().numpy())
+        else:
+            flags, _ = self.vad_model(x.cpu())      # TenVad reads the host signal, as without gpu_vad
+        return flags, e20.cpu().numpy(), dev_wav
+
+    def front_decisions(self, flags, e20, dev_wav):
+        """Post-processing, boundary refinement and chunking from flags and hop energies alone
+        (``vad_post.segments_from_flags`` / ``refine_intervals``); sets the ``last_vad_*`` fields and
+        returns the chunks."""
+        from speakerlab import _hip
+        L = int(dev_wav.shape[0])
+        hop = int(self.vad_frame_size_ms * self.fs / 1000)
+        processed_flags = vad_post.post_process_speech_flags(
+            flags, self.vad_min_speech_ms, self.vad_max_silence_ms, self.vad_frame_size_ms)
+        processed = vad_post.segments_from_flags(processed_flags, L, hop)
+        refined = vad_post.refine_intervals(e20, L, processed, self.fs, self.vad_energy_threshold,
+                                            self.vad_boundary_expansion_ms, self.vad_boundary_energy_percentile)
+        self.last_vad_time_raw = vad_post.flags_to_intervals(flags, L, hop, self.fs)
+        self.last_vad_time_processed = vad_post.intervals_to_seconds(processed, self.fs)
+        self.last_vad_time = vad_time = vad_post.intervals_to_seconds(refined, self.fs)
+        self.last_vad_processed_mask = lambda: vad_post.intervals_to_mask(processed, L)
+        self.last_vad_refined_mask = lambda: vad_post.intervals_to_mask(refined, L)
+        self.last_vad_masked_audio = lambda: _hip.vad_apply_intervals(
+            dev_wav, [s for s, _ in refined], [e for _, e in refined]).cpu().numpy().reshape(1, -1)
+        if self.no_chunk_after_vad:
+            return [[st, ed] for st, ed in vad_time]
+        return [c for st, ed in vad_time for c in self.chunk(st, ed)]
+
     def defer(self, wav, wav_fs=None):
         """``__call__`` up to the clustering, for ``--ahc_batch``: returns a job holding the chunks,
         the embeddings, their cosine affinity (left on the device) and this file's ``last_vad_*``
@@ -254,6 +348,7 @@ class Diarization3Dspeaker:
         chunks, wav_data = self.do_front(wav, wav_fs)
         job = {'chunks': chunks, 'embeddings': None, 'affinity': None,
                'vad': {k: v for k, v in vars(self).items() if k.startswith('last_vad_')}}
+        # (with gpu_vad the unread lazy fields keep this file's device signal alive until then)
         if chunks:
             job['embeddings'] = self.do_emb_extraction(chunks, wav_data)
             X = torch.as_tensor(np.ascontiguousarray(job['embeddings'], dtype=np.float32)).to(self.device)
@@ -476,7 +571,7 @@ def main_process(rank, nprocs, args, wav_list, port=None):
         args.vad_boundary_expansion_ms, args.vad_boundary_energy_percentile, args.vad_threshold,
         args.cluster_mer_cos, args.cluster_fix_cos_thr, args.cluster_min_cluster_size, args.chunk_dur,
         args.chunk_step, args.batch_size, synthetic_weights=args.synthetic_weights, vad=args.vad, group=group,
-        gpu_resample=args.gpu_resample, gpu_ahc=args.gpu_ahc)
+        gpu_resample=args.gpu_resample, gpu_ahc=args.gpu_ahc, gpu_vad=args.gpu_vad)
     # one file per process, as the reference (:924); with --shard_chunks every rank takes part
     # in every file and rank 0 writes the outputs
     mine = wav_list if group is not None else wav_list[rank::nprocs]

@@ -62,18 +62,20 @@ def _is_gpu(device) -> bool:
     return device is not None and torch.device(device).type == 'cuda'
 
 
-def _resample_gpu(waveform: torch.Tensor, orig_freq: int, new_freq: int, device) -> torch.Tensor:
+def _resample_gpu(waveform: torch.Tensor, orig_freq: int, new_freq: int, device, keep_on_device=False) -> torch.Tensor:
     """``resample`` through the HIP kernel (_hip.resample): upload, resample, and hand the result
-    back where and as the host path would (same device, dtype and leading shape)."""
+    back where and as the host path would (same device, dtype and leading shape);
+    ``keep_on_device``: leave it on ``device`` instead."""
     from speakerlab import _hip
     shape = waveform.size()
     x = waveform.reshape(-1, shape[-1]).to(torch.device(device), torch.float32)
     y = _hip.resample(x, int(orig_freq), int(new_freq))
-    return y.reshape(shape[:-1] + (y.shape[-1],)).to(waveform.device, waveform.dtype)
+    y = y.reshape(shape[:-1] + (y.shape[-1],))
+    return y.to(waveform.dtype) if keep_on_device else y.to(waveform.device, waveform.dtype)
 
 
 def resample(waveform: torch.Tensor, orig_freq: int, new_freq: int, lowpass_filter_width: int = 6,
-             rolloff: float = 0.99, device=None) -> torch.Tensor:
+             rolloff: float = 0.99, device=None, keep_on_device=False) -> torch.Tensor:
     """torchaudio.functional.resample(waveform, orig_freq, new_freq) with its defaults: any
     leading shape, time last; output length ceil(new * L / orig) in gcd-reduced rates.
 
@@ -81,7 +83,8 @@ def resample(waveform: torch.Tensor, orig_freq: int, new_freq: int, lowpass_filt
     built in double, so closer to the exact formula than this fp32 host path); the result comes
     back with the waveform's placement, dtype and shape.  The kernel implements the default
     filter only, and refuses rate pairs whose polyphase table is above its cap: both cases
-    take the host path."""
+    take the host path.  ``keep_on_device``: a result the HIP resampler produced stays on
+    ``device`` (the host path's result stays where the waveform is)."""
     if orig_freq <= 0 or new_freq <= 0:
         raise ValueError('Original frequency and desired frequecy should be positive')
     if orig_freq == new_freq:
@@ -89,7 +92,7 @@ def resample(waveform: torch.Tensor, orig_freq: int, new_freq: int, lowpass_filt
     if _is_gpu(device) and lowpass_filter_width == 6 and rolloff == 0.99 and waveform.is_floating_point():
         from speakerlab import _hip
         try:
-            return _resample_gpu(waveform, orig_freq, new_freq, device)
+            return _resample_gpu(waveform, orig_freq, new_freq, device, keep_on_device)
         except _hip.HipError as e:
             if e.code != _hip.E_UNSUPPORTED:
                 raise
@@ -107,18 +110,20 @@ def resample(waveform: torch.Tensor, orig_freq: int, new_freq: int, lowpass_filt
     return y[..., :target].reshape(shape[:-1] + (min(target, y.shape[-1]),))
 
 
-def _resample(wav: torch.Tensor, fs: int, obj_fs: int, device=None) -> torch.Tensor:
-    return resample(wav, fs, obj_fs, device=device)
+def _resample(wav: torch.Tensor, fs: int, obj_fs: int, device=None, keep_on_device=False) -> torch.Tensor:
+    return resample(wav, fs, obj_fs, device=device, keep_on_device=keep_on_device)
 
 
-def load_audio(input, ori_fs=None, obj_fs=None, device=None):
+def load_audio(input, ori_fs=None, obj_fs=None, device=None, keep_on_device=False):
     """``device`` (opt-in, a ROCm device): audio at another rate than ``obj_fs`` is resampled
-    there (``resample``); the result is the CPU [1, L'] tensor of the host path either way."""
+    there (``resample``); the result is the CPU [1, L'] tensor of the host path either way, unless
+    ``keep_on_device`` is set: then a signal the HIP resampler produced is returned where it is, as
+    a [1, L'] tensor on ``device`` (audio that is not resampled there comes back as without it)."""
     if isinstance(input, str):
         wav, fs = read_wav(input)
         wav = wav.mean(dim=0, keepdim=True)
         if obj_fs is not None and fs != obj_fs:
-            wav = _resample(wav, fs, obj_fs, device)
+            wav = _resample(wav, fs, obj_fs, device, keep_on_device)
         return wav
     if isinstance(input, (np.ndarray, torch.Tensor)):
         wav = torch.from_numpy(input) if isinstance(input, np.ndarray) else input
@@ -133,6 +138,6 @@ def load_audio(input, ori_fs=None, obj_fs=None, device=None):
         if wav.ndim == 1:
             wav = wav.unsqueeze(0)
         if ori_fs is not None and obj_fs is not None and ori_fs != obj_fs:
-            wav = _resample(wav, ori_fs, obj_fs, device)
+            wav = _resample(wav, ori_fs, obj_fs, device, keep_on_device)
         return wav
     return input

@@ -123,6 +123,125 @@ def refine_boundaries(audio, vad_mask, fs=16000, energy_threshold=0.05, expansio
     return refined.astype(np.float32)
 
 
+def segments_from_flags(processed_flags, n_samples: int, hop: int):
+    """The runs of ``flags_to_mask(processed_flags, n_samples, hop)`` as ``[start, end)`` sample
+    pairs (0/1 flags, the last frame clipped to the audio), without the mask."""
+    f = np.asarray(processed_flags)
+    if f.size == 0:
+        return []
+    s, e, v = _runs((f != 0).astype(np.int8))
+    s, e = s[v == 1] * hop, np.minimum(e[v == 1] * hop, n_samples)
+    return [[a, b] for a, b in zip(s.tolist(), e.tolist()) if b > a]
+
+
+def _slice_percentile(c, n20, E, s, e, percentile):
+    """``np.percentile(fe[s:e], percentile)`` of every segment, read from the hop-level track.
+
+    ``fe`` is non-decreasing on [0, E) and zero on [E, L), so the sorted slice is its zeros followed
+    by its other samples in place, and the two order statistics the 'linear' method interpolates
+    between are read from ``c`` by index.  The interpolation restates numpy's for a float32 array
+    operation by operation (``numpy/lib/_function_base_impl.py``: ``percentile``, ``_quantile``,
+    ``_get_indexes``, ``_get_gamma``, ``_lerp``), in its dtypes: ``q`` and the virtual index
+    ``(n - 1) * q`` are float32, ``gamma`` is a float64 difference cast to float32, the result
+    is ``a + (b - a) * gamma``, or ``b - (b - a) * (1 - gamma)`` from ``gamma >= 0.5``, in float32.
+    ``tests/test_vad_front_host.py`` pins it to the installed numpy's bits."""
+    n = e - s
+    q = np.float32(np.true_divide(percentile, np.float32(100)))
+    nm1 = (n - 1).astype(np.float32)
+    vi = nm1 * q
+    above = vi >= nm1                                   # takes the largest value
+    prev = np.where(above, n - 1, np.floor(vi).astype(np.int64))
+    nxt = np.where(above, n - 1, prev + 1)
+    gamma = (vi.astype(np.float64) - np.where(above, -1, prev).astype(np.float64)).astype(np.float32)
+    zeros = np.maximum(0, e - np.maximum(s, E))         # the slice's samples in the zero tail sort first
+
+    def order_stat(k):
+        hop = np.clip((s + k - zeros) // 160, 0, n20 - 1)
+        return np.where(k < zeros, np.float32(0), c[hop])
+
+    a, b = order_stat(prev), order_stat(nxt)
+    d = b - a
+    return np.where(gamma >= np.float32(0.5), b - d * (np.float32(1) - gamma), a + d * gamma)
+
+
+def refine_intervals(e20, n_samples, segments, fs=16000, energy_threshold=0.05, expansion_ms=10.0, percentile=10.0):
+    """``refine_boundaries`` at run-length granularity: the runs of ones (``[[s, e], ...]`` sample
+    pairs) of ``refine_boundaries(audio, mask, ...)`` for the mask whose runs are ``segments``,
+    from the hop-level energies ``e20`` (the ``en`` of ``frame_energy``, float32
+    [(L - 320) // 160 + 1]) alone.  Nothing of the audio's length is allocated.
+
+    With ``c = np.maximum.accumulate(e20)`` the per-sample track is ``fe[i] = c[min(i // 160,
+    n20 - 1)]`` for ``i < E = (n20 - 1) * 160 + 320`` and 0 on the tail of fewer than 160 samples
+    past it: non-decreasing, then zero.  Per segment that leaves few cases, all reproduced:
+      - the threshold is the percentile of the per-sample slice (``_slice_percentile``), floored;
+      - the forward look (100 ms) finds its first sample below the threshold either at ``start``
+        itself or, a non-decreasing track having none later, at ``E`` when the window reaches the
+        zero tail;
+      - the backward look finds the last such sample at ``end - 1`` when the segment covers the zero
+        tail, else at the end of the last hop of the window whose value is below the threshold;
+      - the re-expansion starts at ``i + 1``, which leaves the one-sample hole at ``i``;
+      - ``end <= start`` is skipped; ``n20 <= 0`` returns the segments unchanged."""
+    seg = np.asarray(segments, dtype=np.int64).reshape(-1, 2)
+    seg = seg[seg[:, 1] > seg[:, 0]]
+    c = np.maximum.accumulate(np.asarray(e20, dtype=np.float32))
+    n20 = len(c)
+    if n20 <= 0 or len(seg) == 0:
+        return seg.tolist()
+    hop = int(0.01 * fs)
+    if int(0.02 * fs) != 2 * hop or hop != 160:
+        raise ValueError('energy track assumes 20 ms windows at a 10 ms hop of 16 kHz audio')
+    s, e = seg[:, 0], seg[:, 1]
+    E = (n20 - 1) * hop + 2 * hop
+    look = 10 * hop
+    expand = int(expansion_ms * fs / 1000.0)
+    # max(np.percentile(...), floor) compares in float32 and so does every `fe < th` after it
+    th = np.maximum(_slice_percentile(c, n20, E, s, e, percentile).astype(np.float32), np.float32(energy_threshold))
+    zero_lt = np.float32(0) < th
+    # forward: fe[start] itself, or the first sample of the zero tail
+    at_start = np.where(s < E, c[np.minimum(s // hop, n20 - 1)] < th, zero_lt)
+    wend = np.minimum(e, s + look)
+    new_start = np.where(~at_start & (s < E) & (wend > E) & zero_lt, E, s)
+    # backward: over [lo, end)
+    lo = np.maximum(new_start, e - look) + 1
+    can = lo < e
+    tail_hit = can & (e > E) & zero_lt
+    m = np.minimum(e, E)                                # [lo, m): the non-decreasing part of the window
+    mono = can & ~tail_hit & (lo < m)
+    h_lo = np.minimum(lo // hop, n20 - 1)
+    h_hi = np.minimum((m - 1) // hop, n20 - 1)
+    hops = h_lo[:, None] + np.arange(look // hop + 2)[None]
+    below = (c[np.minimum(hops, n20 - 1)] < th[:, None]) & (hops <= h_hi[:, None]) & mono[:, None]
+    cnt = below.sum(axis=1)                             # c is non-decreasing: the hops below th come first
+    h_last = h_lo + cnt - 1
+    mono_hit = mono & (cnt > 0)
+    i_mono = np.minimum(m, np.where(h_last < n20 - 1, (h_last + 1) * hop, E)) - 1
+    hit = tail_hit | mono_hit
+    i = np.where(tail_hit, e - 1, i_mono)
+    first = np.maximum(s, new_start - expand) if expand > 0 else new_start
+    out = []
+    for a, b, h, k in zip(first.tolist(), e.tolist(), hit.tolist(), i.tolist()):
+        if not h:
+            out.append([a, b])
+            continue
+        out.append([a, k])
+        if expand > 0 and k + 1 < b:
+            out.append([k + 1, b])
+    return out
+
+
+def intervals_to_mask(intervals, n_samples: int) -> np.ndarray:
+    """Per-sample float32 mask whose runs of ones are the ``[start, end)`` sample pairs."""
+    mask = np.zeros(n_samples, dtype=np.float32)
+    for a, b in intervals:
+        mask[a:b] = 1.0
+    return mask
+
+
+def intervals_to_seconds(intervals, fs=16000):
+    """``mask_to_intervals`` of the mask whose runs are the sample pairs: the same divisions and filter."""
+    return [[s / fs, e / fs] for s, e in intervals if e / fs > s / fs]
+
+
 def mask_to_intervals(mask, fs=16000):
     if len(mask) == 0:
         return []

@@ -18,6 +18,9 @@
  *                        FbankComputer::compute_feature runtime/onnxruntime/feature/feature_fbank.cpp:22-91
  *   spk_resample_f32     torchaudio.functional.resample as called by load_audio,
  *                        speakerlab/utils/fileio.py:105-129
+ *   spk_vad_energy_f32, spk_vad_apply_intervals_f32
+ *                        the per-sample numpy of speakerlab/bin/infer_diarization.py's VAD front:
+ *                        the frame energies (:403-413 and the VAD's own) and the masked copy (:560-601)
  *   spk_model_create     model construction + strict load_state_dict in
  *                        speakerlab/bin/infer_sv_batch.py:247-253 (and the ONNX session
  *                        runtime/onnxruntime/model/speaker_embedding_model.cpp:7-40)
@@ -141,6 +144,41 @@ int spk_resample_taps(int32_t orig_freq, int32_t new_freq, int32_t* n_phases, in
  * ranges is written; the output buffer has the layout spk_fbank_f32 reads. */
 int spk_resample_f32(const float* wav, const int64_t* wav_offsets, int32_t n_utt, int32_t orig_freq,
                      int32_t new_freq, float* out, const int64_t* out_offsets, void* stream);
+
+/* VAD front end of the diarization pipeline, 16 kHz only: the O(L) arithmetic in front of the
+ * frame- and segment-level decisions, which stay on the host (speakerlab/utils/vad_post.py).
+ *
+ * spk_vad_energy_f32: one pass over a ragged batch (wav device float32, offsets DEVICE int64
+ * [n_utt+1], the convention of spk_fbank_f32 / spk_resample_f32).  Every sample is first clipped
+ * to [-1, 1]; per utterance of length L two mean-square tracks are written:
+ *   e16 (device float64) [L / 256]: every non-overlapping 16 ms frame, the quantity under the
+ *       energy VAD's 10 log10(. + 1e-12);
+ *   e20 (device float32) [n20], n20 = (L - 320) / 160 + 1 for L >= 320, else 0: every 20 ms window
+ *       at a 10 ms hop, the `en` of vad_post.frame_energy.
+ * e16_offsets[u+1]-e16_offsets[u] and e20_offsets[u+1]-e20_offsets[u] must equal spk_vad_energy_sizes
+ * of utterance u.  Squares and sums are fp64 in a fixed order counted from the utterance's own first
+ * sample (quads of 4 samples, blocks of 32 = 8 quads, a hop = 5 blocks, a frame = 8 blocks, each
+ * added in ascending order, no FMA contraction), e16 = frame / 256.0 and
+ * e20[j] = float(hop[j] + hop[j+1]) / 320.0f, so an utterance has the same bits alone and inside any
+ * batch.  Utterances shorter than a frame / a window write nothing to that track; nothing outside
+ * the declared ranges is written.  Non-finite samples are outside the contract: np.clip propagates
+ * a NaN, the kernel's fminf / fmaxf do not.  Enqueues only.
+ *
+ * spk_vad_apply_intervals_f32: out[i] = wav[i] for i inside one of the n_iv intervals
+ * [starts[k], ends[k]) (DEVICE int64, sorted, disjoint, within [0, L]), else 0: the device form of
+ * vad_post.apply_mask on the unclipped signal.  n_iv == 0 zeroes the output (starts / ends may then
+ * be NULL); L == 0 launches nothing.  Enqueues only.
+ *
+ * Errors: n_utt < 0, L < 0, n_iv < 0 or a null pointer SPK_E_INVALID (spk_vad_energy_f32 with
+ * n_utt == 0 succeeds and launches nothing); an e16 that is not 8-byte aligned SPK_E_INVALID; a
+ * library built without the kernels SPK_E_UNSUPPORTED from the two launching entries.  Nothing is
+ * written on an error. */
+/* L / 256 and (L - 320) / 160 + 1 (0 below 320): host arithmetic, no GPU needed. */
+int spk_vad_energy_sizes(int64_t L, int64_t* n16, int64_t* n20);
+int spk_vad_energy_f32(const float* wav, const int64_t* wav_offsets, int32_t n_utt, double* e16,
+                       const int64_t* e16_offsets, float* e20, const int64_t* e20_offsets, void* stream);
+int spk_vad_apply_intervals_f32(const float* wav, int64_t L, const int64_t* starts, const int64_t* ends,
+                                int64_t n_iv, float* out, void* stream);
 
 /* Build a handle on the CURRENT HIP device: folds BatchNorm into conv weights, packs them
  * for the kernels and uploads them (synchronous, once per model). */

@@ -5,7 +5,7 @@ sub-segments -> GPU Fbank + ERes2NetV2 embeddings -> clustering (the CLI's AHC b
 the spectral back-end of the recipes) -> merged segments.  Prints one JSON line with the
 time of every stage and the real-time factor.
 
-    python tools/bench_diarization.py [--minutes 60] [--batch 256] [--cluster ahc|spectral|both]
+    python tools/bench_diarization.py [--minutes 60] [--batch 256] [--cluster ahc|spectral|both] [--gpu_vad]
 """
 import argparse
 import json
@@ -28,6 +28,8 @@ def main():
     ap.add_argument('--speakers', type=int, default=4)
     ap.add_argument('--batch', type=int, default=256)
     ap.add_argument('--cluster', choices=['ahc', 'spectral', 'both'], default='both')
+    ap.add_argument('--gpu_vad', action='store_true',
+                    help='time the VAD front through the device path (Diarization3Dspeaker(gpu_vad=True))')
     args = ap.parse_args()
     from speakerlab.bin import infer_diarization as idz
     from speakerlab.process import cluster
@@ -38,16 +40,34 @@ def main():
     wav, turns = synthetic.synth_meeting(args.minutes * 60, args.speakers, seed=3)
     t['synth_s'] = time.perf_counter() - t0
 
-    diar = idz.Diarization3Dspeaker('cuda', synthetic_weights=True, vad='energy', batch_size=args.batch)
+    diar = idz.Diarization3Dspeaker('cuda', synthetic_weights=True, vad='energy', batch_size=args.batch,
+                                    gpu_vad=args.gpu_vad)
     wt = torch.from_numpy(wav)[None]
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    flags, x = diar.do_vad(wt)
-    t['vad_s'] = time.perf_counter() - t0
-    t0 = time.perf_counter()
-    _, _, vad_time = diar.postprocess_vad(flags, x)
-    chunks = [c for st, ed in vad_time for c in diar.chunk(st, ed)]
-    t['vad_post_and_chunk_s'] = time.perf_counter() - t0
+    front_equal = None
+    if args.gpu_vad:
+        # the same two stages through the device front: vad_s is the upload, the energy kernel, the
+        # copy of the two tracks and the flags; vad_post_and_chunk_s everything up to the chunks
+        diar.front_energies(torch.from_numpy(wav[:16000])[None])     # warm-up: library load, first launch
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        flags, e20, dev_wav = diar.front_energies(wt)
+        t['vad_s'] = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        chunks = diar.front_decisions(flags, e20, dev_wav)
+        t['vad_post_and_chunk_s'] = time.perf_counter() - t0
+        vad_time = diar.last_vad_time
+        host_flags, x = diar.do_vad(wt)                               # untimed: the host front on the same input
+        front_equal = diar.postprocess_vad(host_flags, x)[2] == vad_time
+        wt = dev_wav[None]                                            # the embeddings read the device signal
+    else:
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        flags, x = diar.do_vad(wt)
+        t['vad_s'] = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        _, _, vad_time = diar.postprocess_vad(flags, x)
+        chunks = [c for st, ed in vad_time for c in diar.chunk(st, ed)]
+        t['vad_post_and_chunk_s'] = time.perf_counter() - t0
     diar.do_emb_extraction(chunks[:args.batch], wt)     # warm-up (plan + graph capture)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -55,7 +75,10 @@ def main():
     torch.cuda.synchronize()
     t['embeddings_s'] = time.perf_counter() - t0
     res = {'workload': 'c5', 'audio_s': round(len(wav) / 16000, 1), 'speakers': args.speakers,
-           'vad_segments': len(vad_time), 'chunks': len(chunks), 'embed_batch': args.batch}
+           'vad_segments': len(vad_time), 'chunks': len(chunks), 'embed_batch': args.batch,
+           'gpu_vad': bool(args.gpu_vad)}
+    if front_equal is not None:
+        res['front_intervals_equal'] = bool(front_equal)   # refined intervals == the host front's on this input
     # DER against the generator's ground-truth turns, scored like the reference recipe
     # (egs/.../local/DER.py + md-eval.pl: collar 0, overlap scored; speakerlab/utils/der.py)
     ref_rttm = [f'SPEAKER meeting 0 {st:.3f} {ed - st:.3f} <NA> <NA> spk{k} <NA> <NA>' for st, ed, k in turns]
