@@ -30,4 +30,12 @@ hipError_t launch_fbank(const float* wav, const int64_t* wav_off, int n_utt, flo
                         const int64_t* frame_off, int n_mels, int mean_nor, const FbankTables* tab,
                         int mel_nb, hipStream_t s, int t_max = 0);
 
+// Circle-padded chunks of one device signal (spk_fbank_chunks_f32): chunk c is the samples
+// wav[chunk_start[c] + i % chunk_len[c]], i < pad_len, and gives `frames` = 1 + (pad_len - 400) / 160
+// rows at feats[c * frames]; the same kernel with the wrap in its sample addresses (fbank.hip).
+// Not linked into the host-only build of the executor (tests/emu): weak, checked by the ABI.
+hipError_t launch_fbank_chunks(const float* wav, const int64_t* chunk_start, const int64_t* chunk_len, int n_chunks,
+                               int frames, float* feats, int n_mels, int mean_nor, const FbankTables* tab,
+                               int mel_nb, hipStream_t s) __attribute__((weak));
+
 }  // namespace spk

@@ -136,6 +136,21 @@ __device__ __forceinline__ void dft8(double* re, double* im) {
 // frames at a time.  Workgroup id -> (utterance, slice) is XCD-aware: all slices of
 // utterance u run on XCD u % 8 (dispatch is round-robin over the 8 XCDs), which is also
 // where fbank_cmn_kernel's workgroup u runs, so the rows it re-reads are in that XCD's L2.
+//
+// CHUNKS (spk_fbank_chunks_f32): utterance u is the circle-padded chunk u of the signal `wav`,
+// sample i of it is wav[wav_off[u] + i % frame_off[u]] (wav_off holds the chunk starts,
+// frame_off the chunk lengths), every chunk has t_max frames and its rows are at u * t_max.
+// Only the sample addresses of step 1 differ, so the rows have the bits of the packed kernel
+// on the materialised [n_utt, pad_len] batch.  The wrap costs no per-sample division:
+//   n >= 400: one reduction per frame pair (r = 320 p mod n, wave-uniform); a lane's first
+//             index r + lane < n + 64 and every step of 64 (and the 160 to frame b) stay
+//             below 2 n, so each takes one conditional subtraction;
+//   n <  400: the chunk wraps several times inside one frame: each lane reduces its first
+//             index (r + lane) mod n once per frame (32-bit), then steps by 64 mod n < n, again
+//             with one conditional subtraction per sample.
+// A chunk longer than the frames reach (400 + 160 (t_max - 1) samples) never wraps; its length
+// is clamped to that, which keeps every index in 32 bits.
+template <bool CHUNKS>
 __global__ void __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(4)))
 fbank_frames_kernel(const float* __restrict__ wav, const int64_t* __restrict__ wav_off,
                     float* __restrict__ feats, const int64_t* __restrict__ frame_off,
@@ -149,12 +164,15 @@ fbank_frames_kernel(const float* __restrict__ wav, const int64_t* __restrict__ w
   if (utt >= n_utt) return;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const float* x = wav + wav_off[utt];
-  const int nfr = (int)(frame_off[utt + 1] - frame_off[utt]);
+  const int nfr = CHUNKS ? t_max : (int)(frame_off[utt + 1] - frame_off[utt]);
   // packed (t_max == 0): rows at frame_off[utt]; padded: rows at utt * t_max, rows
   // [nfr, t_max) of the utterance zeroed
   const int64_t f0 = t_max > 0 ? (int64_t)utt * t_max : frame_off[utt];
   float* out = feats + f0 * n_mels;
-  if (t_max > 0)
+  // CHUNKS: the chunk's length, at most the samples its frames read (>= 1 by contract)
+  unsigned cn = 1;
+  if constexpr (CHUNKS) cn = (unsigned)std::min<int64_t>(frame_off[utt], (int64_t)FLEN + (int64_t)FSHIFT * (t_max - 1));
+  if (!CHUNKS && t_max > 0)
     for (int e = nfr * n_mels + g * blockDim.x + threadIdx.x; e < t_max * n_mels; e += G * blockDim.x) out[e] = 0.f;
 
   double2* wb = buf[wave];
@@ -178,13 +196,42 @@ fbank_frames_kernel(const float* __restrict__ wav, const int64_t* __restrict__ w
     float xa[8], xb[8];
     double re[8], im[8];
     double suma = 0.0, sumb = 0.0;
+    if constexpr (CHUNKS) {
+      // ia / ib: this lane's index into the chunk for frame a / b, always in [0, cn)
+      const unsigned r = (unsigned)(fa * FSHIFT) % cn;
+      unsigned ia, ib, step;
+      if (cn >= (unsigned)FLEN) {
+        ia = r + lane;
+        ia -= ia >= cn ? cn : 0u;
+        ib = ia + FSHIFT;
+        ib -= ib >= cn ? cn : 0u;
+        step = 64;
+      } else {
+        ia = (r + lane) % cn;
+        ib = (r + FSHIFT + lane) % cn;
+        step = 64u % cn;
+      }
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int i = lane + 64 * j;
-      xa[j] = i < FLEN ? sa[i] : 0.f;
-      xb[j] = (hasb && i < FLEN) ? sb[i] : 0.f;
-      suma += (double)xa[j];
-      sumb += (double)xb[j];
+      for (int j = 0; j < 8; ++j) {
+        const int i = lane + 64 * j;
+        xa[j] = i < FLEN ? x[ia] : 0.f;
+        xb[j] = (hasb && i < FLEN) ? x[ib] : 0.f;
+        suma += (double)xa[j];
+        sumb += (double)xb[j];
+        ia += step;
+        ia -= ia >= cn ? cn : 0u;
+        ib += step;
+        ib -= ib >= cn ? cn : 0u;
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int i = lane + 64 * j;
+        xa[j] = i < FLEN ? sa[i] : 0.f;
+        xb[j] = (hasb && i < FLEN) ? sb[i] : 0.f;
+        suma += (double)xa[j];
+        sumb += (double)xb[j];
+      }
     }
     const double ma = wave_sum_d(suma) * (1.0 / FLEN), mb = wave_sum_d(sumb) * (1.0 / FLEN);
     FB_STAMP(0);
@@ -317,14 +364,15 @@ fbank_frames_kernel(const float* __restrict__ wav, const int64_t* __restrict__ w
 // the fp32 rows fbank_frames_kernel wrote: column sums in double in a fixed order (row
 // lanes, then a fixed-order LDS reduction), then x - mean rounded once.  One workgroup per
 // utterance on XCD u % 8, where the rows still sit in L2.  Columns as float4 when n_mels %
-// 4 == 0 (V = 4), else scalar.
-template <int V>
+// 4 == 0 (V = 4), else scalar.  UNIFORM (chunks): every utterance has t_max rows and there is
+// no frame_off array.
+template <int V, bool UNIFORM = false>
 __global__ void __launch_bounds__(1024)
 fbank_cmn_kernel(float* __restrict__ feats, const int64_t* __restrict__ frame_off, int n_mels, int t_max) {
   __shared__ double red[1024 * V];
   __shared__ double mean[128];
   const int utt = blockIdx.x;
-  const int nfr = (int)(frame_off[utt + 1] - frame_off[utt]);
+  const int nfr = UNIFORM ? t_max : (int)(frame_off[utt + 1] - frame_off[utt]);
   if (nfr <= 0) return;
   const int64_t f0 = t_max > 0 ? (int64_t)utt * t_max : frame_off[utt];
   float* out = feats + f0 * n_mels;
@@ -375,25 +423,40 @@ fbank_cmn_kernel(float* __restrict__ feats, const int64_t* __restrict__ frame_of
   }
 }
 
-}  // namespace
-
-hipError_t launch_fbank(const float* wav, const int64_t* wav_off, int n_utt, float* feats,
-                        const int64_t* frame_off, int n_mels, int mean_nor, const FbankTables* tab,
-                        int mel_nb, hipStream_t s, int t_max) {
+// chunks: wav_off = chunk starts, frame_off = chunk lengths, t_max = frames of every chunk
+template <bool CHUNKS>
+hipError_t launch_fbank_t(const float* wav, const int64_t* wav_off, int n_utt, float* feats,
+                          const int64_t* frame_off, int n_mels, int mean_nor, const FbankTables* tab,
+                          int mel_nb, hipStream_t s, int t_max) {
   if (n_mels <= 0 || n_mels > 128 || n_utt < 0 || t_max < 0 || mel_nb <= 0 || mel_nb % 16) return hipErrorInvalidValue;
   if (n_utt == 0) return hipSuccess;
   // slices per utterance: about 16k waves in the grid (4 per SIMD of 4 x 256), at least one
   // workgroup per utterance, at most 64 (a 5 s utterance has 249 frame pairs)
   const int G = std::max(1, std::min(64, 16384 / (WAVES * n_utt)));
   const int groups = (n_utt + 7) / 8;
-  hipLaunchKernelGGL(fbank_frames_kernel, dim3(8 * G * groups), dim3(64 * WAVES), 0, s, wav, wav_off, feats,
+  hipLaunchKernelGGL(fbank_frames_kernel<CHUNKS>, dim3(8 * G * groups), dim3(64 * WAVES), 0, s, wav, wav_off, feats,
                      frame_off, tab, n_mels, mel_nb, t_max, n_utt, G);
   if (hipError_t e = hipGetLastError(); e != hipSuccess || !mean_nor) return e;
   if (n_mels % 4 == 0)
-    hipLaunchKernelGGL(fbank_cmn_kernel<4>, dim3(n_utt), dim3(1024), 0, s, feats, frame_off, n_mels, t_max);
+    hipLaunchKernelGGL((fbank_cmn_kernel<4, CHUNKS>), dim3(n_utt), dim3(1024), 0, s, feats, frame_off, n_mels, t_max);
   else
-    hipLaunchKernelGGL(fbank_cmn_kernel<1>, dim3(n_utt), dim3(1024), 0, s, feats, frame_off, n_mels, t_max);
+    hipLaunchKernelGGL((fbank_cmn_kernel<1, CHUNKS>), dim3(n_utt), dim3(1024), 0, s, feats, frame_off, n_mels, t_max);
   return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_fbank(const float* wav, const int64_t* wav_off, int n_utt, float* feats,
+                        const int64_t* frame_off, int n_mels, int mean_nor, const FbankTables* tab,
+                        int mel_nb, hipStream_t s, int t_max) {
+  return launch_fbank_t<false>(wav, wav_off, n_utt, feats, frame_off, n_mels, mean_nor, tab, mel_nb, s, t_max);
+}
+
+hipError_t launch_fbank_chunks(const float* wav, const int64_t* chunk_start, const int64_t* chunk_len, int n_chunks,
+                               int frames, float* feats, int n_mels, int mean_nor, const FbankTables* tab,
+                               int mel_nb, hipStream_t s) {
+  if (frames < 1) return hipErrorInvalidValue;
+  return launch_fbank_t<true>(wav, chunk_start, n_chunks, feats, chunk_len, n_mels, mean_nor, tab, mel_nb, s, frames);
 }
 
 #if SPK_FB_PROF

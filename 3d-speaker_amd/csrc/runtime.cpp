@@ -507,6 +507,33 @@ int spk_version(void) { return 2; }   // include/spk_hip.h: ABI revision
 
 const char* spk_last_error(void) { return g_last_error.c_str(); }
 
+// the device's Fbank tables for n_mels (built and uploaded on first use, rebuilt when n_mels
+// changes); `unsupported`: the code for an n_mels the tables cannot be built for
+static int fbank_tables(const char* who, int32_t n_mels, int unsupported, FbankTables** tab, int* mel_nb) {
+  int dev = 0;
+  if (int rc = hip_check(hipGetDevice(&dev), "hipGetDevice")) return rc;
+  if (dev < 0 || dev >= 64) return SPK_E_DEVICE;
+  std::lock_guard<std::mutex> lk(g_tables_mu);
+  if (!g_tables[dev] || g_tables_mels[dev] != n_mels) {
+    FbankTables host;
+    std::memset(&host, 0, sizeof(host));
+    if (build_fbank_tables(&host, n_mels, 16000.0) < 0) {
+      set_error(std::string(who) + ": unsupported n_mels");
+      return unsupported;
+    }
+    if (!g_tables[dev]) {
+      if (int rc = hip_check(hipMalloc(&g_tables[dev], sizeof(FbankTables)), "hipMalloc(fbank tables)")) return rc;
+    }
+    if (int rc = hip_check(hipMemcpy(g_tables[dev], &host, sizeof(host), hipMemcpyHostToDevice), "hipMemcpy"))
+      return rc;
+    g_tables_mels[dev] = n_mels;
+    g_tables_nb[dev] = host.mel_nb;
+  }
+  *tab = g_tables[dev];
+  *mel_nb = g_tables_nb[dev];
+  return SPK_OK;
+}
+
 static int fbank_impl(const float* wav, const int64_t* wav_offsets, int32_t n_utt, float* feats,
                       const int64_t* frame_offsets, int32_t n_mels, int32_t mean_nor, void* stream, int32_t t_max) {
   return guarded([&]() -> int {
@@ -514,31 +541,9 @@ static int fbank_impl(const float* wav, const int64_t* wav_offsets, int32_t n_ut
       set_error("spk_fbank_f32: invalid argument");
       return SPK_E_INVALID;
     }
-    int dev = 0;
-    if (int rc = hip_check(hipGetDevice(&dev), "hipGetDevice")) return rc;
-    if (dev < 0 || dev >= 64) return SPK_E_DEVICE;
     FbankTables* tab = nullptr;
     int mel_nb = 0;
-    {
-      std::lock_guard<std::mutex> lk(g_tables_mu);
-      if (!g_tables[dev] || g_tables_mels[dev] != n_mels) {
-        FbankTables host;
-        std::memset(&host, 0, sizeof(host));
-        if (build_fbank_tables(&host, n_mels, 16000.0) < 0) {
-          set_error("spk_fbank_f32: unsupported n_mels");
-          return SPK_E_UNSUPPORTED;
-        }
-        if (!g_tables[dev]) {
-          if (int rc = hip_check(hipMalloc(&g_tables[dev], sizeof(FbankTables)), "hipMalloc(fbank tables)")) return rc;
-        }
-        if (int rc = hip_check(hipMemcpy(g_tables[dev], &host, sizeof(host), hipMemcpyHostToDevice), "hipMemcpy"))
-          return rc;
-        g_tables_mels[dev] = n_mels;
-        g_tables_nb[dev] = host.mel_nb;
-      }
-      tab = g_tables[dev];
-      mel_nb = g_tables_nb[dev];
-    }
+    if (int rc = fbank_tables("spk_fbank_f32", n_mels, SPK_E_UNSUPPORTED, &tab, &mel_nb)) return rc;
     return hip_check(launch_fbank(wav, wav_offsets, n_utt, feats, frame_offsets, n_mels, mean_nor, tab, mel_nb,
                                   reinterpret_cast<hipStream_t>(stream), t_max),
                      "fbank launch");
@@ -557,6 +562,37 @@ int spk_fbank_f32_padded(const float* wav, const int64_t* wav_offsets, int32_t n
     return SPK_E_INVALID;
   }
   return fbank_impl(wav, wav_offsets, n_utt, feats, frame_offsets, n_mels, mean_nor, stream, t_max);
+}
+
+int spk_fbank_chunks_f32(const float* wav, int64_t wav_len, const int64_t* chunk_start, const int64_t* chunk_len,
+                         int32_t n_chunks, int64_t pad_len, float* feats, int32_t n_mels, int32_t mean_nor,
+                         void* stream) {
+  return guarded([&]() -> int {
+    auto bad = [](const char* msg) {
+      set_error(std::string("spk_fbank_chunks_f32: ") + msg);
+      return SPK_E_INVALID;
+    };
+    // every check runs on the host before the launch; the start / length arrays are device
+    // memory and are not read here (their contract is the caller's: include/spk_hip.h)
+    if (n_chunks < 0) return bad("n_chunks < 0");
+    if (pad_len < 400) return bad("pad_len < 400 (shorter than one frame)");
+    if (pad_len > INT32_MAX) return bad("pad_len above 2^31 - 1");
+    if (wav_len < 1) return bad("wav_len < 1");
+    if (n_mels <= 3 || n_mels > 128) return bad("unsupported n_mels");
+    if (n_chunks == 0) return SPK_OK;
+    if (!wav || !chunk_start || !chunk_len || !feats) return bad("null pointer");
+    if (!launch_fbank_chunks) {
+      set_error("spk_fbank_chunks_f32: this build of the library has no kernels");
+      return SPK_E_UNSUPPORTED;
+    }
+    FbankTables* tab = nullptr;
+    int mel_nb = 0;
+    if (int rc = fbank_tables("spk_fbank_chunks_f32", n_mels, SPK_E_INVALID, &tab, &mel_nb)) return rc;
+    const int frames = (int)(1 + (pad_len - 400) / 160);
+    return hip_check(launch_fbank_chunks(wav, chunk_start, chunk_len, n_chunks, frames, feats, n_mels, mean_nor, tab,
+                                         mel_nb, reinterpret_cast<hipStream_t>(stream)),
+                     "fbank chunks launch");
+  });
 }
 
 int spk_model_create(const spk_model_config_t* cfg, const spk_weight_t* weights, int32_t n_weights, spk_model_t** out) {

@@ -60,6 +60,8 @@ SYMBOLS = {
     'spk_fbank_f32': (ctypes.c_int, [_P, _P, ctypes.c_int32, _P, _P, ctypes.c_int32, ctypes.c_int32, _P]),
     'spk_fbank_f32_padded': (ctypes.c_int, [_P, _P, ctypes.c_int32, _P, _P, ctypes.c_int32, ctypes.c_int32,
                                             ctypes.c_int32, _P]),
+    'spk_fbank_chunks_f32': (ctypes.c_int, [_P, ctypes.c_int64, _P, _P, ctypes.c_int32, ctypes.c_int64, _P,
+                                            ctypes.c_int32, ctypes.c_int32, _P]),
     'spk_resample_out_len': (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
                                             ctypes.POINTER(ctypes.c_int64)]),
     'spk_resample_taps': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
@@ -127,6 +129,7 @@ _lib = None
 _lock = threading.Lock()
 
 
+E_INVALID = -1       # SPK_E_INVALID
 E_UNSUPPORTED = -6   # SPK_E_UNSUPPORTED
 
 
@@ -237,6 +240,49 @@ def fbank_padded(wavs: torch.Tensor, lengths, n_mels: int = 80, mean_nor: bool =
                                           offs[1].data_ptr(), tmax, n_mels, int(bool(mean_nor)), _stream(dev)),
                'spk_fbank_f32_padded')
     return feats, torch.tensor(frames, dtype=torch.int32).to(dev, non_blocking=True)
+
+
+def _invalid(msg: str):
+    err = HipError(msg)
+    err.code = E_INVALID
+    return err
+
+
+def fbank_chunks(wav: torch.Tensor, starts, lens, pad_len: int, n_mels: int = 80,
+                 mean_nor: bool = False) -> torch.Tensor:
+    """Fbank of circle-padded chunks of a device signal, [n, T, n_mels] with T = 1 + (pad_len - 400)
+    // 160 (spk_fbank_chunks_f32): chunk c is ``wav[starts[c] + arange(pad_len) % lens[c]]``, read in
+    place by the kernel, and the rows have the bits of ``fbank`` on that gathered batch.
+
+    ``wav``: 1-D float32 device tensor (one recording, or several back to back); ``starts`` /
+    ``lens``: n int64 values each, sequences or host or device tensors.  Every chunk must lie inside
+    the signal (``lens >= 1``, ``0 <= starts``, ``starts + lens <= len(wav)``): checked here on the
+    host values (device tensors are copied back for it), ``HipError`` with ``E_INVALID`` otherwise.
+    """
+    require_device_tensor(wav, 'fbank_chunks')
+    if wav.dim() != 1:
+        raise _invalid(f'fbank_chunks: expected a 1-D signal, got {tuple(wav.shape)}')
+    dev = _dev_of(wav)
+    wav = wav.to(torch.float32).contiguous()
+    s = torch.as_tensor(starts, dtype=torch.int64).reshape(-1)
+    n_ = torch.as_tensor(lens, dtype=torch.int64).reshape(-1)
+    n = int(s.numel())
+    if int(n_.numel()) != n:
+        raise _invalid('fbank_chunks: starts and lens differ in length')
+    L, pad_len = int(wav.numel()), int(pad_len)
+    if n:
+        sh, nh = s.cpu(), n_.cpu()
+        if bool((nh < 1).any()) or bool((sh < 0).any()) or bool((sh + nh > L).any()):
+            raise _invalid('fbank_chunks: every chunk needs lens >= 1, starts >= 0 and starts + lens <= len(wav)')
+    if s.device != n_.device:
+        s, n_ = s.to(dev), n_.to(dev)
+    sn = torch.stack([s, n_]).to(dev, non_blocking=True)      # host values: one upload
+    feats = torch.empty((n, max(num_frames(pad_len), 0), n_mels), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _check(lib().spk_fbank_chunks_f32(wav.data_ptr(), L, sn[0].data_ptr(), sn[1].data_ptr(), n, pad_len,
+                                          feats.data_ptr(), n_mels, int(bool(mean_nor)), _stream(dev)),
+               'spk_fbank_chunks_f32')
+    return feats
 
 
 # ----------------------------------------------------------------------------- resampling

@@ -16,7 +16,8 @@ MI355X execution of the stages:
   (``start + j mod len``), then GPU Fbank and the native ERes2NetV2 forward run on batches;
 * the N x N cosine affinity of the clustering runs on the GPU (MFMA), AHC / merging on the
   host as in ``speakerlab.process.cluster`` (``--gpu_ahc``: the AHC loop on the GPU too;
-  ``--ahc_batch K``: one batched AHC launch for K files).
+  ``--ahc_batch K``: one batched AHC launch for K files; ``--pool_chunks``: the K files'
+  sub-segments embedded in shared batches, circle-padded inside the Fbank kernel).
 
 Differences forced by the offline environment (documented in DESIGN.md):
 * TenVad (third-party binary library) is used when importable; otherwise an energy VAD
@@ -79,6 +80,11 @@ parser.add_argument('--gpu_ahc', action='store_true',
 parser.add_argument('--ahc_batch', default=1, type=int, metavar='K',
                     help='MI355X build, with --gpu_ahc: cluster K files with one batched AHC launch (their '
                          'affinities wait on the device); 1: every file on its own')
+parser.add_argument('--pool_chunks', action='store_true',
+                    help='MI355X build, with --ahc_batch K > 1: embed the sub-segments of the K files of a group in '
+                         'shared batches (chunks of files with the same pad length fill a batch together; the HIP '
+                         'Fbank reads them in place from one pooled signal).  A group\'s front-end and embedding '
+                         'time is split evenly over its files in the per-file timing')
 parser.add_argument('--gpu_vad', action='store_true',
                     help='MI355X build: compute the VAD front end\'s frame energies and the masked audio on the '
                          'GPU (HIP kernels) and refine the boundaries from run lengths; the signal is uploaded '
@@ -355,6 +361,26 @@ class Diarization3Dspeaker:
             job['affinity'] = _hip.cosine_affinity(X)
         return job
 
+    def defer_many(self, wavs, wav_fs=None):
+        """``defer`` for a group of files, with their sub-segments embedded in shared batches
+        (``--pool_chunks``): the front end of every file, one pooled extraction, then each file's
+        affinity.  Returns the jobs ``[defer(w) for w in wavs]`` would, for ``finish_deferred`` /
+        ``restore_deferred``."""
+        from speakerlab import _hip
+        jobs, signals = [], []
+        for wav in wavs:
+            chunks, wav_data = self.do_front(wav, wav_fs)
+            jobs.append({'chunks': chunks, 'embeddings': None, 'affinity': None,
+                         'vad': {k: v for k, v in vars(self).items() if k.startswith('last_vad_')}})
+            signals.append(wav_data)
+        embeddings = self.do_emb_extraction_pooled([job['chunks'] for job in jobs], signals)
+        for job, emb in zip(jobs, embeddings):
+            if job['chunks']:
+                job['embeddings'] = emb
+                X = torch.as_tensor(np.ascontiguousarray(emb, dtype=np.float32)).to(self.device)
+                job['affinity'] = _hip.cosine_affinity(X)
+        return jobs
+
     def finish_deferred(self, jobs, speaker_num=None):
         """Cluster the jobs of ``defer`` with one ``from_affinities`` call; sets each job's
         ``'segments'`` (what ``__call__`` returns for that file)."""
@@ -437,6 +463,41 @@ class Diarization3Dspeaker:
         lo, hi = bounds[rank]
         local = self.embed_batches(dev_wav, starts, lens, max_len, lo, hi)
         return all_gather_rows(local, [e - s for s, e in bounds], self.group).cpu().numpy()
+
+    def do_emb_extraction_pooled(self, chunks_per_file, wavs):
+        """``do_emb_extraction`` of several files at once: their signals are concatenated into one
+        device pool, every sub-segment keeps its file's pad length (that file's longest one, as in
+        ``do_emb_extraction``), and sub-segments padded alike share batches of ``batchsize``
+        (``chunk_pool.plan_chunk_batches``).  The Fbank kernel circle-pads in its addressing
+        (``FBank.chunks``), so no padded copy is built.  Returns one [n_f, D] array per file, None
+        for a file without chunks."""
+        from speakerlab.utils.chunk_pool import plan_chunk_batches
+        starts, lens, parts, base = [], [], [], 0
+        for chunks, wav in zip(chunks_per_file, wavs):
+            x = wav[0] if wav.dim() == 2 else wav
+            L = int(x.shape[0])
+            st = np.asarray([min(int(a * self.fs), L) for a, _ in chunks], dtype=np.int64)
+            ln = np.asarray([min(int(b * self.fs), L) for _, b in chunks], dtype=np.int64) - st
+            if ln.size and int(ln.min()) <= 0:
+                raise ValueError('empty sub-segment')
+            starts.append(st + base)              # offsets into the pool
+            lens.append(ln)
+            if chunks:                            # a file without chunks adds nothing to the pool
+                parts.append(x.to(self.device, torch.float32))
+                base += L
+        batches, inverse = plan_chunk_batches(lens, self.batchsize)
+        if not batches:
+            return [None] * len(wavs)
+        pool = parts[0] if len(parts) == 1 else torch.cat(parts)
+        out = []
+        with torch.no_grad():
+            for b in batches:
+                s = np.asarray([starts[f][c] for f, c in zip(b.files, b.chunks)], dtype=np.int64)
+                n = np.asarray([lens[f][c] for f, c in zip(b.files, b.chunks)], dtype=np.int64)
+                feats = self.feature_extractor.chunks(pool, torch.from_numpy(s), torch.from_numpy(n), b.pad_len)
+                out.append(self.embedding_model(feats))
+        rows = torch.cat(out).cpu().numpy()
+        return [rows[inv] if len(inv) else None for inv in inverse]
 
     def do_clustering(self, chunks, embeddings, speaker_num=None):
         spk = speaker_num if speaker_num is not None else self.speaker_num
@@ -579,6 +640,7 @@ def main_process(rank, nprocs, args, wav_list, port=None):
         from tqdm import tqdm
         mine = tqdm(mine, desc='Rank 0 processing')
     pending = []   # --ahc_batch K > 1: (wav_path, job, seconds so far) of files not yet clustered
+    group_paths = []   # --pool_chunks: the files of the group being collected
 
     def flush():
         t0 = time.time()
@@ -589,6 +651,15 @@ def main_process(rank, nprocs, args, wav_list, port=None):
             diar.restore_deferred(job)
             write_outputs(wav_path, spent + share + time.time() - t0)
         pending.clear()
+
+    def pool_group():
+        # one defer_many for the group; its time is split evenly over the files
+        t0 = time.time()
+        jobs = diar.defer_many(group_paths)
+        share = (time.time() - t0) / len(group_paths)
+        pending.extend((wav_path, job, share) for wav_path, job in zip(group_paths, jobs))
+        group_paths.clear()
+        flush()
 
     def write_outputs(wav_path, elapsed):
         wav_id = os.path.basename(wav_path).rsplit('.', 1)[0]
@@ -603,6 +674,11 @@ def main_process(rank, nprocs, args, wav_list, port=None):
 
     for wav_path in mine:
         t0 = time.time()
+        if args.pool_chunks:
+            group_paths.append(wav_path)
+            if len(group_paths) == args.ahc_batch:
+                pool_group()
+            continue
         if args.ahc_batch > 1:
             pending.append((wav_path, diar.defer(wav_path), time.time() - t0))
             if len(pending) == args.ahc_batch:
@@ -613,6 +689,8 @@ def main_process(rank, nprocs, args, wav_list, port=None):
         if group is not None and rank != 0:
             continue
         write_outputs(wav_path, elapsed)
+    if group_paths:
+        pool_group()                              # a trailing group smaller than K
     if pending:
         flush()                                   # a trailing group smaller than K
     if group is not None:
@@ -631,6 +709,8 @@ def main(argv=None):
         parser.error('--ahc_batch needs --gpu_ahc: the batched AHC runs on the GPU.')
     if args.ahc_batch > 1 and args.shard_chunks:
         parser.error('--ahc_batch clusters whole files per rank and cannot be combined with --shard_chunks.')
+    if args.pool_chunks and args.ahc_batch <= 1:
+        parser.error('--pool_chunks pools the files of an --ahc_batch group: it needs --ahc_batch K > 1.')
     if args.wav.endswith('.wav'):
         wav_list = [args.wav]
     else:

@@ -75,3 +75,11 @@ class FBank(object):
         if back is None:
             return out
         return [o.to(back) for o in out] if isinstance(out, list) else out.to(back)
+
+    def chunks(self, wav: torch.Tensor, starts, lens, pad_len: int):
+        """[n, T, n_mels] of the chunks ``wav[starts[c] + arange(pad_len) % lens[c]]`` of the 1-D
+        signal ``wav``, circle-padded in the kernel's addressing: what ``batch`` gives for that
+        gathered [n, pad_len] batch, bit for bit (``_hip.fbank_chunks``)."""
+        dev_wav, back = self._on_device(wav)
+        out = _hip.fbank_chunks(dev_wav, starts, lens, pad_len, self.n_mels, self.mean_nor)
+        return out if back is None else out.to(back)

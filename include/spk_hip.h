@@ -106,7 +106,9 @@ typedef struct {
   int32_t reserved[6];
 } spk_model_config_t;
 
-/* ABI revision: 2 (spk_model_range_check's seven-argument form, spk_model_config_t.pooling) */
+/* ABI revision: 2 (spk_model_range_check's seven-argument form, spk_model_config_t.pooling), additive
+ * level 1: spk_fbank_chunks_f32.  Entries are only ever added inside a revision, so spk_version()
+ * still returns 2; a caller that needs an added entry looks its symbol up. */
 int spk_version(void);
 const char* spk_last_error(void);
 
@@ -121,6 +123,26 @@ int spk_fbank_f32(const float* wav, const int64_t* wav_offsets, int32_t n_utt, f
  * The input of spk_model_forward_lengths for variable-length batches. */
 int spk_fbank_f32_padded(const float* wav, const int64_t* wav_offsets, int32_t n_utt, float* feats,
                          const int64_t* frame_offsets, int32_t t_max, int32_t n_mels, int32_t mean_nor, void* stream);
+
+/* Fbank of circle-padded chunks of one device signal, without materialising them: the
+ * circle_pad of the diarization pipeline's sub-segment extraction (speakerlab/bin/
+ * infer_diarization.py do_emb_extraction) done in the kernel's own addressing.
+ *   wav          device float32 [wav_len]: one recording, or several back to back;
+ *   chunk_start, chunk_len  DEVICE int64 [n_chunks];
+ *   sample i of chunk c, 0 <= i < pad_len, is wav[chunk_start[c] + i % chunk_len[c]];
+ *   feats        device [n_chunks, T, n_mels], T = 1 + (pad_len - 400) / 160.
+ * The rows have exactly the bits spk_fbank_f32 writes for the gathered [n_chunks, pad_len] batch
+ * (same kernel, same arithmetic in the same order; only the sample addresses differ).
+ * Enqueues only.  The two arrays are not read on the host, so their contract is the caller's:
+ * every chunk must satisfy chunk_len >= 1, chunk_start >= 0 and chunk_start + chunk_len <= wav_len;
+ * anything else reads outside the signal.  (speakerlab._hip.fbank_chunks checks it on its host
+ * copies before the upload.)  SPK_E_INVALID: n_chunks < 0, pad_len < 400 or above 2^31 - 1,
+ * wav_len < 1, n_mels outside [4, 128] or one the mel tables cannot be built for, a null pointer
+ * with n_chunks > 0.  n_chunks == 0: SPK_OK, nothing is launched.  SPK_E_UNSUPPORTED: a host-only
+ * build of the library without kernels. */
+int spk_fbank_chunks_f32(const float* wav, int64_t wav_len, const int64_t* chunk_start, const int64_t* chunk_len,
+                         int32_t n_chunks, int64_t pad_len, float* feats, int32_t n_mels, int32_t mean_nor,
+                         void* stream);
 
 /* Sample-rate conversion in front of the Fbank: torchaudio.functional.resample with its defaults
  * (Hann-windowed sinc, lowpass_filter_width 6, rolloff 0.99), the resampler behind the reference's
