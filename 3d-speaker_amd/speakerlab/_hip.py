@@ -7,6 +7,7 @@ is imported by tests only.)
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import os
 import threading
@@ -123,6 +124,12 @@ SYMBOLS = {
     'spk_cosine_cohort_stats': (ctypes.c_int, [_P, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
                                                _P, _P, _P, ctypes.c_size_t, _P]),
     'spk_cosine_trials_norm': (ctypes.c_int, [_P, _P, ctypes.c_int32, _P, _P, ctypes.c_int64, _P, _P, _P, _P, _P, _P]),
+    'spk_pair_cosine_sizes': (ctypes.c_int, [ctypes.POINTER(ctypes.c_int64), ctypes.c_int32,
+                                             ctypes.POINTER(ctypes.c_int64)]),
+    'spk_pair_cosine_stats': (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64),
+                                             ctypes.c_int32, ctypes.c_float, _P, _P, _P, _P, _P, _P]),
+    'spk_pair_cosine_plan': (ctypes.c_int, [ctypes.POINTER(ctypes.c_int64), ctypes.c_int32, ctypes.c_int32]
+                             + [ctypes.POINTER(ctypes.c_int64)] * 4),
 }
 
 _lib = None
@@ -962,3 +969,83 @@ def cosine_trials_norm(a: torch.Tensor, b: torch.Tensor, ia: torch.Tensor, ib: t
                                             ia.numel(), st[0].data_ptr(), st[1].data_ptr(), st[2].data_ptr(),
                                             st[3].data_ptr(), out.data_ptr(), _stream(dev)), 'spk_cosine_trials_norm')
     return out
+
+
+# ----------------------------------------------------------------------------- pair-cosine statistics
+PAIR_MAX_ROWS = 32768         # largest group (kPairMaxRows)
+PAIR_FUSED_MAX_ROWS = 4096    # largest group without a cosine array (kPairFusedMaxRows)
+PairStats = collections.namedtuple('PairStats', ['cos', 'min', 'mean', 'argmin', 'n_below', 'pair_offsets'])
+
+
+def pair_cosine_sizes(offsets):
+    """Prefix sums of the pair counts n (n - 1) / 2 of the groups ``offsets`` delimits (G + 1 row
+    offsets starting at 0): where each group's condensed cosines start in ``pair_cosine_stats``'s
+    ``cos`` (spk_pair_cosine_sizes; host arithmetic, no GPU needed)."""
+    offs = [int(v) for v in offsets]
+    if not offs:
+        raise _invalid('pair_cosine_sizes: offsets needs at least the leading 0')
+    G = len(offs) - 1
+    out = (ctypes.c_int64 * (G + 1))()
+    _check(lib().spk_pair_cosine_sizes((ctypes.c_int64 * (G + 1))(*offs), G, out), 'spk_pair_cosine_sizes')
+    return list(out)
+
+
+def pair_cosine_stats(X: torch.Tensor, offsets, threshold: float, want_cos: bool = True) -> PairStats:
+    """Statistics of the pair cosines inside every group of rows of ``X`` (spk_pair_cosine_stats).
+
+    ``X``: [N, E] float32 device tensor (a view with a row stride above E is read in place when the
+    stride is a multiple of 4); ``offsets``: G + 1 host integers, group g is rows
+    ``offsets[g]:offsets[g + 1]``.  Returns ``PairStats`` of device tensors: ``cos`` float32, every
+    group's pair cosines in ``np.triu_indices(n, 1)`` order back to back (None without
+    ``want_cos``), ``min`` / ``mean`` float32 [G], ``argmin`` int64 [G] (condensed index inside the
+    group, smallest among equals, -1 below two rows), ``n_below`` int64 [G] (cosines strictly below
+    ``threshold``), and ``pair_offsets``, the host list of where each group starts in ``cos``.  A
+    cosine has the bits ``cosine_trials`` gives for the two rows; a group's results have the same
+    bits alone and in any batch, with and without ``want_cos``.  A view the kernels cannot read in
+    place (a row stride that is no multiple of 4, rows that are not 16-byte aligned, another dtype)
+    is copied first.  Without ``want_cos`` the library takes groups of up to
+    ``PAIR_FUSED_MAX_ROWS`` rows; for a larger one the cosines go to a scratch array here and are
+    dropped (the same statistics)."""
+    require_device_tensor(X, 'pair_cosine_stats')
+    if X.dim() != 2:
+        raise _invalid(f'pair_cosine_stats: expected [N, E], got {tuple(X.shape)}')
+    dev = _dev_of(X)
+    N, E = int(X.shape[0]), int(X.shape[1])
+    if X.dtype != torch.float32 or (N and (X.stride(1) != 1 or X.stride(0) < E or X.stride(0) % 4
+                                           or X.data_ptr() % 16)):
+        X = X.to(torch.float32).contiguous()
+        if X.data_ptr() % 16:
+            X = X.clone()               # contiguous already, but off a 16-byte boundary: a fresh block
+    ldx = int(X.stride(0)) if N > 1 else E
+    offs = [int(v) for v in offsets]
+    if not offs or offs[-1] > N:
+        raise _invalid(f'pair_cosine_stats: offsets must start at 0 and end within the {N} rows of X')
+    G = len(offs) - 1
+    po = pair_cosine_sizes(offs)
+    with_cos = want_cos or any(b - a > PAIR_FUSED_MAX_ROWS for a, b in zip(offs, offs[1:]))
+    cos = torch.empty(po[-1], dtype=torch.float32, device=dev) if with_cos else None
+    mn = torch.empty(G, dtype=torch.float32, device=dev)
+    mean = torch.empty(G, dtype=torch.float32, device=dev)
+    argmin = torch.empty(G, dtype=torch.int64, device=dev)
+    below = torch.empty(G, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        _check(lib().spk_pair_cosine_stats(X.data_ptr() if N else None, ldx, E, (ctypes.c_int64 * (G + 1))(*offs), G,
+                                           float(threshold), cos.data_ptr() if with_cos and po[-1] else None,
+                                           mn.data_ptr() if G else None, mean.data_ptr() if G else None,
+                                           argmin.data_ptr() if G else None, below.data_ptr() if G else None,
+                                           _stream(dev)), 'spk_pair_cosine_stats')
+    return PairStats(cos if want_cos else None, mn, mean, argmin, below, po)
+
+
+def pair_cosine_plan(offsets, with_cos: bool = True) -> dict:
+    """The launches ``pair_cosine_stats`` makes for these row offsets (spk_pair_cosine_plan; host
+    arithmetic, no GPU needed): ``pair_launches`` and ``stats_launches``, ``max_launch_pairs`` (the
+    most pairs one pair launch covers; a pair takes a wave of 64 work-items and a grid holds fewer
+    than 2^32) and ``planned_pairs`` (the pairs all pair launches cover together)."""
+    offs = [int(v) for v in offsets]
+    if not offs:
+        raise _invalid('pair_cosine_plan: offsets needs at least the leading 0')
+    vals = [ctypes.c_int64() for _ in range(4)]
+    _check(lib().spk_pair_cosine_plan((ctypes.c_int64 * len(offs))(*offs), len(offs) - 1, int(bool(with_cos)),
+                                      *[ctypes.byref(v) for v in vals]), 'spk_pair_cosine_plan')
+    return dict(zip(('pair_launches', 'stats_launches', 'max_launch_pairs', 'planned_pairs'), (v.value for v in vals)))

@@ -464,13 +464,14 @@ class Diarization3Dspeaker:
         local = self.embed_batches(dev_wav, starts, lens, max_len, lo, hi)
         return all_gather_rows(local, [e - s for s, e in bounds], self.group).cpu().numpy()
 
-    def do_emb_extraction_pooled(self, chunks_per_file, wavs):
+    def do_emb_extraction_pooled(self, chunks_per_file, wavs, keep_on_device=False):
         """``do_emb_extraction`` of several files at once: their signals are concatenated into one
         device pool, every sub-segment keeps its file's pad length (that file's longest one, as in
         ``do_emb_extraction``), and sub-segments padded alike share batches of ``batchsize``
         (``chunk_pool.plan_chunk_batches``).  The Fbank kernel circle-pads in its addressing
         (``FBank.chunks``), so no padded copy is built.  Returns one [n_f, D] array per file, None
-        for a file without chunks."""
+        for a file without chunks; with ``keep_on_device`` the arrays are device tensors and nothing
+        is copied to the host."""
         from speakerlab.utils.chunk_pool import plan_chunk_batches
         starts, lens, parts, base = [], [], [], 0
         for chunks, wav in zip(chunks_per_file, wavs):
@@ -496,7 +497,13 @@ class Diarization3Dspeaker:
                 n = np.asarray([lens[f][c] for f, c in zip(b.files, b.chunks)], dtype=np.int64)
                 feats = self.feature_extractor.chunks(pool, torch.from_numpy(s), torch.from_numpy(n), b.pad_len)
                 out.append(self.embedding_model(feats))
-        rows = torch.cat(out).cpu().numpy()
+        rows = torch.cat(out)
+        if keep_on_device:
+            # one index upload and one gather for the group, split per file
+            idx = torch.from_numpy(np.concatenate(inverse)).to(self.device)
+            parts = torch.split(rows[idx], [len(inv) for inv in inverse])
+            return [p if len(inv) else None for p, inv in zip(parts, inverse)]
+        rows = rows.cpu().numpy()
         return [rows[inv] if len(inv) else None for inv in inverse]
 
     def do_clustering(self, chunks, embeddings, speaker_num=None):

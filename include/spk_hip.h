@@ -38,6 +38,8 @@
  *   spk_topk_stats, spk_cosine_cohort_stats, spk_cosine_trials_norm
  *                        nothing in the reference: the numpy partition / mean / std of cohort
  *                        scores (S-norm / AS-norm) users write next to compute_score_metrics.py
+ *   spk_pair_cosine_stats    the pair loop of speakerlab/bin/check_single_speaker.py
+ *                        (check_single_speaker: cosine of every segment pair, min and mean)
  */
 #ifndef SPK_HIP_H
 #define SPK_HIP_H
@@ -107,7 +109,8 @@ typedef struct {
 } spk_model_config_t;
 
 /* ABI revision: 2 (spk_model_range_check's seven-argument form, spk_model_config_t.pooling), additive
- * level 1: spk_fbank_chunks_f32.  Entries are only ever added inside a revision, so spk_version()
+ * level 1: spk_fbank_chunks_f32; level 2: spk_pair_cosine_sizes, spk_pair_cosine_stats,
+ * spk_pair_cosine_plan.  Entries are only ever added inside a revision, so spk_version()
  * still returns 2; a caller that needs an added entry looks its symbol up. */
 int spk_version(void);
 const char* spk_last_error(void);
@@ -409,6 +412,51 @@ int spk_cosine_cohort_stats(const float* X, int64_t N, const float* C, int64_t N
 int spk_cosine_trials_norm(const float* Ea, const float* Eb, int32_t E, const int64_t* ia, const int64_t* ib,
                            int64_t n_trials, const float* mean_a, const float* std_a, const float* mean_b,
                            const float* std_b, float* scores, void* stream);
+
+/* Pair-cosine statistics of a ragged batch of embedding groups: the arithmetic of the reference's
+ * speakerlab/bin/check_single_speaker.py (every segment pair's cosine, their minimum and mean) for
+ * many files in one call.  X: device float32 [N_total, E], row stride ldx, 16-byte aligned rows;
+ * offsets: HOST int64 [G + 1], offsets[0] = 0, non-decreasing; group g is rows offsets[g] ..
+ * offsets[g + 1], n_g of them, P_g = n_g (n_g - 1) / 2 pairs.
+ *
+ * spk_pair_cosine_sizes (host arithmetic, no GPU needed): pair_offsets (HOST int64 [G + 1]), the
+ * prefix sums of P_g.
+ *
+ * spk_pair_cosine_stats, outputs on the device:
+ *   cos      float32 [pair_offsets[G]] or NULL: group g's pair cosines at cos[pair_offsets[g] ..], in
+ *            condensed upper-triangle row-major order (0,1), (0,2), ..., (1,2), ... (the order of
+ *            np.triu_indices(n, 1)); each is the value, bit for bit, spk_cosine_trials gives for the
+ *            two rows (sklearn semantics, a zero-norm row divides by 1 and scores 0);
+ *   min      float32 [G]; argmin int64 [G]: the condensed index of the minimum inside the group,
+ *            the smallest one among equal values;
+ *   mean     float32 [G]: the fp64 sum of the fp32 cosines, in an order fixed by the pairs' condensed
+ *            indices alone, divided by P_g and rounded once;
+ *   n_below  int64 [G]: pairs with cosine < threshold (strictly);
+ *   a group with n_g <= 1: min = mean = 1.0 (the reference's rule), argmin = -1, n_below = 0.
+ *   a NaN cosine (a non-finite row) orders below every number: min is NaN, argmin the first NaN,
+ *   the mean NaN, as numpy's min / argmin / mean of the cosines; it is never below the threshold.
+ * A group's outputs have the same bits alone and inside any batch, with and without cos.  With cos
+ * the pairs are scored by one wave each across the device, in launches of at most 2^25 pairs (a
+ * grid is a 32-bit count of work-items, and a pair takes a wave), and a workgroup per group reduces
+ * them; with cos == NULL one workgroup per group does both, which suits the tool's groups of tens
+ * of rows and is capped at 4096 rows per group.  Enqueues only (the offsets travel as kernel
+ * arguments, 64 groups per launch).  G == 0 succeeds and launches nothing; without any pair only
+ * the statistics' launch runs.
+ * Errors, all checked before the first launch: a null pointer (cos excepted; X only when there are
+ * rows), G < 0, E not a positive multiple of 4, ldx < E or not a multiple of 4, an X that is not
+ * 16-byte aligned, offsets[0] != 0 or decreasing offsets SPK_E_INVALID; a group above the cap of
+ * 32768 rows (4096 with cos == NULL), or a library built without the kernels, SPK_E_UNSUPPORTED.
+ * Nothing is written on an error.
+ *
+ * spk_pair_cosine_plan (host arithmetic, diagnostics and tests): the launches spk_pair_cosine_stats
+ * makes for these offsets, from the plan it walks itself: the number of pair launches (0 without
+ * cos) and of statistics launches, the most pairs one pair launch covers, and the pairs all of
+ * them cover together (pair_offsets[G] with cos). */
+int spk_pair_cosine_sizes(const int64_t* offsets, int32_t G, int64_t* pair_offsets);
+int spk_pair_cosine_stats(const float* X, int64_t ldx, int32_t E, const int64_t* offsets, int32_t G, float threshold,
+                          float* cos, float* min, float* mean, int64_t* argmin, int64_t* n_below, void* stream);
+int spk_pair_cosine_plan(const int64_t* offsets, int32_t G, int32_t with_cos, int64_t* n_pair_launches,
+                         int64_t* n_stats_launches, int64_t* max_launch_pairs, int64_t* planned_pairs);
 
 #ifdef __cplusplus
 }
