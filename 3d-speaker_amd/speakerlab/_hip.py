@@ -130,6 +130,14 @@ SYMBOLS = {
                                              ctypes.c_int32, ctypes.c_float, _P, _P, _P, _P, _P, _P]),
     'spk_pair_cosine_plan': (ctypes.c_int, [ctypes.POINTER(ctypes.c_int64), ctypes.c_int32, ctypes.c_int32]
                              + [ctypes.POINTER(ctypes.c_int64)] * 4),
+    'spk_cosine_sim_workspace_bytes': (ctypes.c_int, [ctypes.c_int64] + [ctypes.POINTER(ctypes.c_size_t)] * 3),
+    'spk_cosine_rows_topk': (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, _P, _P,
+                                            _P, _P, ctypes.c_size_t, _P]),
+    'spk_cosine_triu_stats': (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int32, _P, ctypes.c_int32, _P, ctypes.c_int32,
+                                             ctypes.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t,
+                                             _P, ctypes.c_size_t, _P]),
+    'spk_cosine_triu_hist': (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int32, _P, ctypes.c_int32, ctypes.c_int32, _P,
+                                            _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P, ctypes.c_size_t, _P]),
 }
 
 _lib = None
@@ -1049,3 +1057,130 @@ def pair_cosine_plan(offsets, with_cos: bool = True) -> dict:
     _check(lib().spk_pair_cosine_plan((ctypes.c_int64 * len(offs))(*offs), len(offs) - 1, int(bool(with_cos)),
                                       *[ctypes.byref(v) for v in vals]), 'spk_pair_cosine_plan')
     return dict(zip(('pair_launches', 'stats_launches', 'max_launch_pairs', 'planned_pairs'), (v.value for v in vals)))
+
+
+# ----------------------------------------------------------------------------- corpus similarity statistics
+_sim_ws: Dict = {}   # (device index, stream handle) -> (workspace, state), grown on demand like the cohort's
+
+
+def cosine_sim_workspace_bytes(n: int):
+    """(smallest, recommended, state) bytes of the corpus similarity entries for n rows: one block of
+    128 rows of scores, blocks of about 128 MiB, and the triangle entries' device state."""
+    lo, rec, st = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
+    _check(lib().spk_cosine_sim_workspace_bytes(int(n), ctypes.byref(lo), ctypes.byref(rec), ctypes.byref(st)),
+           'spk_cosine_sim_workspace_bytes')
+    return lo.value, rec.value, st.value
+
+
+def _sim_buffers(dev, n: int, workspace_bytes):
+    """The cached (workspace, its size to pass, state) of the current stream of ``dev``."""
+    _, rec, st_bytes = cosine_sim_workspace_bytes(n)
+    need = rec if workspace_bytes is None else int(workspace_bytes)
+    key = (dev.index, _stream(dev))
+    ws, st = _sim_ws.get(key, (None, None))
+    if ws is None or ws.numel() < need or st.numel() < st_bytes:
+        _sim_ws.pop(key, None)   # free the old blocks before the larger ones
+        del ws, st
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+        st = torch.empty(st_bytes, dtype=torch.uint8, device=dev)
+        _sim_ws[key] = (ws, st)
+    return ws, need, st
+
+
+def sim_release_workspace():
+    """Drop the cached similarity-statistics workspaces (up to about 128 MiB per stream)."""
+    _sim_ws.clear()
+
+
+def _sim_input(x: torch.Tensor, what: str):
+    require_device_tensor(x, what)
+    if x.dim() != 2 or x.shape[0] < 1:
+        raise _invalid(f'{what}: expected [N, E] with N >= 1, got {tuple(x.shape)}')
+    return x.to(torch.float32).contiguous(), _dev_of(x)
+
+
+def cosine_rows_topk(x: torch.Tensor, k: int, workspace_bytes: Optional[int] = None) -> dict:
+    """Per row of the cosine matrix of ``x`` [N, E] against itself, over the other columns
+    (spk_cosine_rows_topk; the matrix is produced and consumed in row blocks, never as a whole):
+    ``top_scores`` [N, k] float32 and ``top_index`` [N, k] int64, score descending then column
+    ascending, -inf / -1 where N - 1 < k; ``sum``, ``sumsq`` float64 [N]; ``min``, ``max``, ``self``
+    float32 [N].  Device tensors.  k in 1..1024."""
+    x, dev = _sim_input(x, 'cosine_rows_topk')
+    N, E = x.shape
+    out = dict(top_scores=torch.empty((N, int(k)) if k > 0 else (N, 0), dtype=torch.float32, device=dev),
+               top_index=torch.empty((N, int(k)) if k > 0 else (N, 0), dtype=torch.int64, device=dev),
+               sum=torch.empty(N, dtype=torch.float64, device=dev), sumsq=torch.empty(N, dtype=torch.float64, device=dev),
+               min=torch.empty(N, dtype=torch.float32, device=dev), max=torch.empty(N, dtype=torch.float32, device=dev),
+               self=torch.empty(N, dtype=torch.float32, device=dev))
+    with torch.cuda.device(dev):
+        ws, need, _ = _sim_buffers(dev, N, workspace_bytes)
+        _check(lib().spk_cosine_rows_topk(x.data_ptr(), N, E, int(k), out['top_scores'].data_ptr(),
+                                          out['top_index'].data_ptr(), out['sum'].data_ptr(), out['sumsq'].data_ptr(),
+                                          out['min'].data_ptr(), out['max'].data_ptr(), out['self'].data_ptr(),
+                                          ws.data_ptr(), need, _stream(dev)), 'spk_cosine_rows_topk')
+    return out
+
+
+def cosine_triu_stats(x: torch.Tensor, thresholds=(), ranks=(), n_ext: int = 0, nbins: int = 0, edges=None,
+                      workspace_bytes: Optional[int] = None) -> dict:
+    """Statistics of the P = N (N - 1) / 2 pairs i < j of the cosine matrix of ``x`` [N, E] against
+    itself (spk_cosine_triu_stats, then spk_cosine_triu_hist when a histogram or extreme pairs are
+    asked for; at most five passes over the scores, which are never stored).  Numpy results:
+    ``count``, ``sum``, ``sumsq`` (float64), ``min``, ``max`` (float32), ``count_ge`` int64 per
+    threshold (float32 compares), ``order_stats`` float32 at the 0-based ascending ``ranks``;
+    with ``nbins`` > 0 ``hist`` int64 over ``edges`` (float64 [nbins + 1]; default
+    ``np.linspace(float64 min, float64 max, nbins + 1)``, widened by 0.5 either way when min == max as
+    numpy does), bin b holding edges[b] <= s < edges[b + 1] and the last bin closed; with ``n_ext``
+    > 0 ``most`` and ``least``: (scores float32, i int64, j int64) of the min(n_ext, P) largest pairs,
+    score descending then (i, j) ascending, and the smallest, score ascending then (i, j) ascending.
+    Synchronises the stream."""
+    import numpy as np
+    x, dev = _sim_input(x, 'cosine_triu_stats')
+    N, E = x.shape
+    thr = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float32).reshape(-1))
+    rk = np.ascontiguousarray(np.asarray(ranks, dtype=np.int64).reshape(-1))
+    n_ext, nbins = int(n_ext), int(nbins)
+    count = np.zeros(1, np.int64)
+    sums = np.zeros(2, np.float64)
+    mm = np.zeros(2, np.float32)
+    count_ge = np.zeros(max(len(thr), 1), np.int64)
+    order = np.zeros(max(len(rk), 1), np.float32)
+    cut = np.zeros(2, np.float32)
+    take = np.zeros(2, np.int32)
+    ptr = lambda a: a.ctypes.data
+    with torch.cuda.device(dev):
+        ws, need, st = _sim_buffers(dev, N, workspace_bytes)
+        _check(lib().spk_cosine_triu_stats(x.data_ptr(), N, E, ptr(thr) if len(thr) else None, len(thr),
+                                           ptr(rk) if len(rk) else None, len(rk), n_ext, ptr(count), ptr(sums),
+                                           ptr(sums) + 8, ptr(mm), ptr(mm) + 4, ptr(count_ge), ptr(order), ptr(cut),
+                                           ptr(take), ws.data_ptr(), need, st.data_ptr(), st.numel(), _stream(dev)),
+               'spk_cosine_triu_stats')
+        out = dict(count=int(count[0]), sum=float(sums[0]), sumsq=float(sums[1]), min=mm[0], max=mm[1],
+                   count_ge=count_ge[:len(thr)].copy(), order_stats=order[:len(rk)].copy())
+        if nbins <= 0 and n_ext <= 0:
+            return out
+        if nbins > 0:
+            if edges is None:
+                lo, hi = (float(mm[0]), float(mm[1])) if count[0] else (0.0, 1.0)
+                if lo == hi:
+                    lo, hi = lo - 0.5, hi + 0.5
+                edges = np.linspace(lo, hi, nbins + 1)
+            edges = np.ascontiguousarray(np.asarray(edges, dtype=np.float64).reshape(-1))
+            if len(edges) != nbins + 1:
+                raise _invalid(f'cosine_triu_stats: {nbins} bins need {nbins + 1} edges, got {len(edges)}')
+            out['edges'] = edges
+        hist = np.zeros(max(nbins, 1), np.int64)
+        es = np.zeros((2, max(n_ext, 1)), np.float32)
+        ei = np.zeros((2, max(n_ext, 1)), np.int64)
+        ej = np.zeros((2, max(n_ext, 1)), np.int64)
+        found = np.zeros(2, np.int32)
+        _check(lib().spk_cosine_triu_hist(x.data_ptr(), N, E, ptr(edges) if nbins > 0 else None, max(nbins, 0), n_ext,
+                                          ptr(cut), ptr(take), ptr(hist), ptr(es), ptr(ei), ptr(ej), ptr(found),
+                                          ws.data_ptr(), need, st.data_ptr(), st.numel(), _stream(dev)),
+               'spk_cosine_triu_hist')
+    if nbins > 0:
+        out['hist'] = hist[:nbins].copy()
+    if n_ext > 0:
+        out['most'] = tuple(a[0, :found[0]].copy() for a in (es, ei, ej))
+        out['least'] = tuple(a[1, :found[1]].copy() for a in (es, ei, ej))
+    return out

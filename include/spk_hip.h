@@ -110,7 +110,8 @@ typedef struct {
 
 /* ABI revision: 2 (spk_model_range_check's seven-argument form, spk_model_config_t.pooling), additive
  * level 1: spk_fbank_chunks_f32; level 2: spk_pair_cosine_sizes, spk_pair_cosine_stats,
- * spk_pair_cosine_plan.  Entries are only ever added inside a revision, so spk_version()
+ * spk_pair_cosine_plan; level 3: spk_cosine_sim_workspace_bytes, spk_cosine_rows_topk,
+ * spk_cosine_triu_stats, spk_cosine_triu_hist.  Entries are only ever added inside a revision, so spk_version()
  * still returns 2; a caller that needs an added entry looks its symbol up. */
 int spk_version(void);
 const char* spk_last_error(void);
@@ -457,6 +458,71 @@ int spk_pair_cosine_stats(const float* X, int64_t ldx, int32_t E, const int64_t*
                           float* cos, float* min, float* mean, int64_t* argmin, int64_t* n_below, void* stream);
 int spk_pair_cosine_plan(const int64_t* offsets, int32_t G, int32_t with_cos, int64_t* n_pair_launches,
                          int64_t* n_stats_launches, int64_t* max_launch_pairs, int64_t* planned_pairs);
+
+/* Corpus similarity statistics: what the reference's
+ * egs/extract_and_comclude_similarities/compute_speaker_similarities_fast.py takes from the N x N
+ * cosine matrix of one embedding set X [N, E] (device float32, contiguous, 16-byte aligned), without
+ * that matrix ever existing.  Score (i, j) is, bit for bit, the value spk_cosine_affinity(X, X)
+ * writes at [i][j] (sklearn semantics: a zero-norm row divides by 1).  As in
+ * spk_cosine_cohort_stats, blocks of R rows against all N columns are scored into the caller's
+ * workspace and consumed in turn, R the largest multiple of 128 the workspace holds.
+ * spk_cosine_sim_workspace_bytes gives the smallest workspace (128 * N * 4 bytes), the recommended
+ * one (blocks of about 128 MiB, which stay in the Infinity Cache between the kernel that writes
+ * them and the ones that read them) and the size of the triangle entries' device state (their
+ * counters, tables and collected pairs; 16-byte aligned, contents undefined between calls).  Every
+ * result has the same bits for every workspace from the smallest up.  No float atomics; every fp64
+ * sum has a fixed order (csrc/sim_stats.hip).  -0.0 and +0.0 are one value throughout and are
+ * reported as +0.0.
+ *
+ * spk_cosine_rows_topk, outputs on the DEVICE, enqueues only.  Per row i, over the columns j != i:
+ *   top_scores float32 [N][k], top_index int64 [N][k]: the k best, score descending then column
+ *              ascending; -inf / -1 from position N - 1 on where N - 1 < k.  k in 1..1024.
+ *   sum, sumsq double [N]; min, max float32 [N] (NaN for N == 1); self float32 [N] = score (i, i).
+ *
+ * spk_cosine_triu_stats and spk_cosine_triu_hist, over the P = N (N - 1) / 2 pairs i < j, each taken
+ * from row i.  Their small inputs and all their outputs are HOST memory, and both SYNCHRONISE the
+ * stream: spk_cosine_triu_stats once per pass of its select (the bins are picked on the host),
+ * spk_cosine_triu_hist once at its end.  Together they make at most five passes over the scores.
+ * spk_cosine_triu_stats:
+ *   count int64 = P; sum, sumsq double; min, max float32;
+ *   count_ge int64 [n_thr]: pairs with score >= thresholds[t], compared in float32; n_thr <= 32;
+ *   order_stats float32 [n_ranks]: the exact order statistics at the 0-based ascending ranks
+ *              (ascending, below P; n_ranks <= 16), by one multi-target MSB-first radix select of
+ *              four 8-bit digit passes, the first one in the same pass as the moments;
+ *   ext_cut float32 [2], ext_take int32 [2]: for n_eff = min(n_ext, P) > 0 the score of the n_eff-th
+ *              largest and of the n_eff-th smallest pair, and how many copies of that score belong to
+ *              the n_eff; two more targets of the same select.  n_ext <= 4096; NaN / 0 for n_ext == 0.
+ *   N == 1: count 0, sum, sumsq, min, max NaN, cuts NaN / 0; nothing is launched.
+ * spk_cosine_triu_hist, one pass:
+ *   hist int64 [nbins] over edges double [nbins + 1] (finite, ascending; nbins <= 256): bin b holds the
+ *              pairs with edges[b] <= (double)s < edges[b + 1], the last bin also s == edges[nbins];
+ *   with n_ext > 0 and ext_cut / ext_take as spk_cosine_triu_stats gave them for the same X and n_ext:
+ *   ext_scores float32 [2][n_ext], ext_i, ext_j int64 [2][n_ext], n_found int32 [2]: row 0 the n_found[0]
+ *              = n_eff largest pairs, score descending then (i, j) ascending; row 1 the n_eff smallest,
+ *              score ascending then (i, j) ascending.  Among equal scores at a cut the first in (i, j)
+ *              order are taken.  Entries from n_found on are not written.
+ *
+ * Errors, all checked before the first launch, nothing written: a null pointer, N < 1, E not a
+ * positive multiple of 4, an X that is not 16-byte aligned, k or n_ext, n_thr, n_ranks, nbins out of
+ * range, a NaN threshold, ranks not ascending or at or above P (so any rank with N == 1), edges not
+ * ascending, cuts that cannot be spk_cosine_triu_stats's SPK_E_INVALID; a workspace below min_bytes or
+ * a state below state_bytes SPK_E_WORKSPACE; N above 2^31 - 1, an N whose single tile of rows would
+ * be a launch of 2^31 work-items or more, or a library built without the kernels
+ * SPK_E_UNSUPPORTED.  spk_cosine_triu_hist also answers SPK_E_INVALID, after its pass and with
+ * nothing written, when the pairs beyond the cuts are not n_eff - ext_take. */
+int spk_cosine_sim_workspace_bytes(int64_t N, size_t* min_bytes, size_t* bytes, size_t* state_bytes);
+int spk_cosine_rows_topk(const float* X, int64_t N, int32_t E, int32_t k, float* top_scores, int64_t* top_index,
+                         double* sum, double* sumsq, float* min, float* max, float* self, void* workspace,
+                         size_t workspace_bytes, void* stream);
+int spk_cosine_triu_stats(const float* X, int64_t N, int32_t E, const float* thresholds, int32_t n_thr,
+                          const int64_t* ranks, int32_t n_ranks, int32_t n_ext, int64_t* count, double* sum,
+                          double* sumsq, float* min, float* max, int64_t* count_ge, float* order_stats, float* ext_cut,
+                          int32_t* ext_take, void* workspace, size_t workspace_bytes, void* state, size_t state_bytes,
+                          void* stream);
+int spk_cosine_triu_hist(const float* X, int64_t N, int32_t E, const double* edges, int32_t nbins, int32_t n_ext,
+                         const float* ext_cut, const int32_t* ext_take, int64_t* hist, float* ext_scores,
+                         int64_t* ext_i, int64_t* ext_j, int32_t* n_found, void* workspace, size_t workspace_bytes,
+                         void* state, size_t state_bytes, void* stream);
 
 #ifdef __cplusplus
 }
