@@ -138,6 +138,11 @@ SYMBOLS = {
                                              _P, ctypes.c_size_t, _P]),
     'spk_cosine_triu_hist': (ctypes.c_int, [_P, ctypes.c_int64, ctypes.c_int32, _P, ctypes.c_int32, ctypes.c_int32, _P,
                                             _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P, ctypes.c_size_t, _P]),
+    'spk_cosine_verif_workspace_bytes': (ctypes.c_int, [ctypes.c_int64] + [ctypes.POINTER(ctypes.c_size_t)] * 3),
+    'spk_cosine_verif_moments': (ctypes.c_int, [_P, _P, ctypes.c_int64, ctypes.c_int32, _P, ctypes.c_int32, _P, _P, _P,
+                                                _P, _P, _P, _P, ctypes.c_size_t, _P, ctypes.c_size_t, _P]),
+    'spk_cosine_verif_digits': (ctypes.c_int, [_P, _P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _P,
+                                               ctypes.c_int32, _P, _P, ctypes.c_size_t, _P, ctypes.c_size_t, _P]),
 }
 
 _lib = None
@@ -1183,4 +1188,100 @@ def cosine_triu_stats(x: torch.Tensor, thresholds=(), ranks=(), n_ext: int = 0, 
     if n_ext > 0:
         out['most'] = tuple(a[0, :found[0]].copy() for a in (es, ei, ej))
         out['least'] = tuple(a[1, :found[1]].copy() for a in (es, ei, ej))
+    return out
+
+
+# ----------------------------------------------------------------------------- all-pairs verification statistics
+_verif_ws: Dict = {}   # (device index, stream handle) -> (workspace, state), grown on demand like _sim_ws
+
+
+def cosine_verif_workspace_bytes(n: int):
+    """(smallest, recommended, state) bytes of the verification entries for n rows: the workspace as
+    for the corpus similarity statistics, and these entries' own device state."""
+    lo, rec, st = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0)
+    _check(lib().spk_cosine_verif_workspace_bytes(int(n), ctypes.byref(lo), ctypes.byref(rec), ctypes.byref(st)),
+           'spk_cosine_verif_workspace_bytes')
+    return lo.value, rec.value, st.value
+
+
+def _verif_buffers(dev, n: int, workspace_bytes):
+    """The cached (workspace, its size to pass, state) of the current stream of ``dev``."""
+    _, rec, st_bytes = cosine_verif_workspace_bytes(n)
+    need = rec if workspace_bytes is None else int(workspace_bytes)
+    key = (dev.index, _stream(dev))
+    ws, st = _verif_ws.get(key, (None, None))
+    if ws is None or ws.numel() < need or st.numel() < st_bytes:
+        _verif_ws.pop(key, None)   # free the old blocks before the larger ones
+        del ws, st
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+        st = torch.empty(st_bytes, dtype=torch.uint8, device=dev)
+        _verif_ws[key] = (ws, st)
+    return ws, need, st
+
+
+def verif_release_workspace():
+    """Drop the cached verification-statistics workspaces (up to about 128 MiB per stream)."""
+    _verif_ws.clear()
+
+
+def _verif_input(x: torch.Tensor, labels: torch.Tensor, what: str):
+    x, dev = _sim_input(x, what)
+    require_device_tensor(labels, what)
+    if labels.dim() != 1 or labels.shape[0] != x.shape[0] or labels.dtype not in (torch.int32, torch.int64):
+        raise _invalid(f'{what}: labels must be an integer tensor of shape [{x.shape[0]}], got '
+                       f'{labels.dtype} {tuple(labels.shape)}')
+    return x, labels.to(device=dev, dtype=torch.int32).contiguous(), dev
+
+
+def cosine_verif_moments(x: torch.Tensor, labels: torch.Tensor, edges=None, workspace_bytes: Optional[int] = None) -> dict:
+    """Per-class statistics of the pairs i < j of the cosine matrix of ``x`` [N, E] against itself
+    (spk_cosine_verif_moments; one pass, the scores are never stored).  Class 1 holds the pairs with
+    ``labels[i] == labels[j]``, class 0 the others.  Numpy results indexed by class: ``count`` int64 [2],
+    ``sum``, ``sumsq`` float64 [2], ``min``, ``max`` float32 [2] (NaN for an empty class), and with
+    ``edges`` (float64 [nbins + 1], nbins <= 256) ``hist`` int64 [2, nbins] with the bins of
+    ``cosine_triu_stats``.  Synchronises the stream."""
+    import numpy as np
+    x, labels, dev = _verif_input(x, labels, 'cosine_verif_moments')
+    N, E = x.shape
+    nbins = 0
+    if edges is not None:
+        edges = np.ascontiguousarray(np.asarray(edges, dtype=np.float64).reshape(-1))
+        nbins = len(edges) - 1
+        if nbins < 1:
+            raise _invalid('cosine_verif_moments: edges need at least two values')
+    count = np.zeros(2, np.int64)
+    sums = np.zeros((2, 2), np.float64)
+    mm = np.zeros((2, 2), np.float32)
+    hist = np.zeros((2, max(nbins, 1)), np.int64)
+    ptr = lambda a: a.ctypes.data
+    with torch.cuda.device(dev):
+        ws, need, st = _verif_buffers(dev, N, workspace_bytes)
+        _check(lib().spk_cosine_verif_moments(x.data_ptr(), labels.data_ptr(), N, E, ptr(edges) if nbins else None, nbins,
+                                              ptr(count), ptr(sums[0]), ptr(sums[1]), ptr(mm[0]), ptr(mm[1]),
+                                              ptr(hist) if nbins else None, ws.data_ptr(), need, st.data_ptr(),
+                                              st.numel(), _stream(dev)), 'spk_cosine_verif_moments')
+    out = dict(count=count, sum=sums[0].copy(), sumsq=sums[1].copy(), min=mm[0].copy(), max=mm[1].copy())
+    if nbins:
+        out['edges'] = edges
+        out['hist'] = hist
+    return out
+
+
+def cosine_verif_digits(x: torch.Tensor, labels: torch.Tensor, level: int, prefixes=(0,),
+                        workspace_bytes: Optional[int] = None):
+    """int64 [n_prefix, 2, 256]: entry [p, c, d] counts the class-c pairs i < j of ``x`` whose 32-bit
+    score key agrees with ``prefixes[p]`` in its top ``level`` bytes (0..3) and whose next byte is d
+    (spk_cosine_verif_digits; one pass, up to 16 prefixes, one empty prefix at level 0).  The
+    primitive of speakerlab/utils/verification_analysis.py.  Synchronises the stream."""
+    import numpy as np
+    x, labels, dev = _verif_input(x, labels, 'cosine_verif_digits')
+    N, E = x.shape
+    pre = np.ascontiguousarray(np.asarray(prefixes, dtype=np.uint32).reshape(-1))
+    out = np.zeros((max(len(pre), 1), 2, 256), np.int64)
+    with torch.cuda.device(dev):
+        ws, need, st = _verif_buffers(dev, N, workspace_bytes)
+        _check(lib().spk_cosine_verif_digits(x.data_ptr(), labels.data_ptr(), N, E, int(level),
+                                             pre.ctypes.data if len(pre) else None, len(pre), out.ctypes.data,
+                                             ws.data_ptr(), need, st.data_ptr(), st.numel(), _stream(dev)),
+               'spk_cosine_verif_digits')
     return out

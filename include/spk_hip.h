@@ -111,7 +111,8 @@ typedef struct {
 /* ABI revision: 2 (spk_model_range_check's seven-argument form, spk_model_config_t.pooling), additive
  * level 1: spk_fbank_chunks_f32; level 2: spk_pair_cosine_sizes, spk_pair_cosine_stats,
  * spk_pair_cosine_plan; level 3: spk_cosine_sim_workspace_bytes, spk_cosine_rows_topk,
- * spk_cosine_triu_stats, spk_cosine_triu_hist.  Entries are only ever added inside a revision, so spk_version()
+ * spk_cosine_triu_stats, spk_cosine_triu_hist; level 4: spk_cosine_verif_workspace_bytes,
+ * spk_cosine_verif_moments, spk_cosine_verif_digits.  Entries are only ever added inside a revision, so spk_version()
  * still returns 2; a caller that needs an added entry looks its symbol up. */
 int spk_version(void);
 const char* spk_last_error(void);
@@ -523,6 +524,48 @@ int spk_cosine_triu_hist(const float* X, int64_t N, int32_t E, const double* edg
                          const float* ext_cut, const int32_t* ext_take, int64_t* hist, float* ext_scores,
                          int64_t* ext_i, int64_t* ext_j, int32_t* n_found, void* workspace, size_t workspace_bytes,
                          void* state, size_t state_bytes, void* stream);
+
+/* All-pairs verification statistics: what exact EER / minDCF / AUC over every labelled pair of one
+ * embedding set need, without the N x N matrix ever existing.  X [N, E] as for the corpus similarity
+ * statistics above (device float32, contiguous, 16-byte aligned), labels int32 [N] on the DEVICE, the
+ * speaker index of each row, none negative.  Pair (i, j), i < j, taken from row i, has class 1 (target)
+ * when labels[i] == labels[j] and class 0 (non-target) otherwise; its score is, bit for bit, what
+ * spk_cosine_affinity(X, X) writes at [i][j], and its key is the order-preserving 32-bit image of
+ * that float (bits b: b == 0x80000000 -> 0 first, so -0.0 and +0.0 share a key; then ~b when the sign
+ * bit is set, b | 0x80000000 otherwise).  The row blocking, the workspace sizes and their meaning
+ * are those of spk_cosine_sim_workspace_bytes; state_bytes is the size of these entries' own device
+ * state (16-byte aligned, contents undefined between calls).  Small inputs and all outputs are HOST
+ * memory; each entry makes one pass over the scores and SYNCHRONISES the stream twice (once for
+ * the labels' check, once at its end).  All counts are exact integers, every result has the same
+ * bits for every workspace from the smallest up, no float atomics, fp64 sums in the fixed order of
+ * csrc/verif_stats.hip.
+ *
+ * spk_cosine_verif_moments, per class c:
+ *   count int64 [2]; sum, sumsq double [2] (0 for an empty class); min, max float32 [2], NaN for an
+ *   empty class;
+ *   hist int64 [2][nbins] over edges double [nbins + 1] (finite, ascending; nbins <= 256, 0: none), bin
+ *              semantics exactly those of spk_cosine_triu_hist.
+ *   N == 1: counts 0, sums, min, max NaN, hist 0; nothing is launched.
+ * spk_cosine_verif_digits, the primitive of the exact searches:
+ *   level in 0..3 and prefixes uint32 [n_prefix], n_prefix in 1..16, of which only the top `level`
+ *              bytes count (level 0: one empty prefix, n_prefix == 1, prefixes may be null);
+ *   digits int64 [n_prefix][2][256]: digits[p][c][d] = the class-c pairs whose key agrees with
+ *              prefix p in its top `level` bytes and whose next byte is d.  Equal prefixes get equal
+ *              rows.  N == 1: zeros.
+ *
+ * Errors: a null pointer, N < 1, E not a positive multiple of 4, an X that is not 16-byte aligned,
+ * nbins, level or n_prefix out of range, edges not finite and ascending, a negative label (found by
+ * a kernel before the pass, nothing written) SPK_E_INVALID; a workspace below min_bytes or a state
+ * below state_bytes SPK_E_WORKSPACE; N above 2^31 - 1, an N whose single tile of rows would be a
+ * launch of 2^31 work-items or more, or a library built without the kernels SPK_E_UNSUPPORTED. */
+int spk_cosine_verif_workspace_bytes(int64_t N, size_t* min_bytes, size_t* bytes, size_t* state_bytes);
+int spk_cosine_verif_moments(const float* X, const int32_t* labels, int64_t N, int32_t E, const double* edges,
+                             int32_t nbins, int64_t* count, double* sum, double* sumsq, float* min, float* max,
+                             int64_t* hist, void* workspace, size_t workspace_bytes, void* state, size_t state_bytes,
+                             void* stream);
+int spk_cosine_verif_digits(const float* X, const int32_t* labels, int64_t N, int32_t E, int32_t level,
+                            const uint32_t* prefixes, int32_t n_prefix, int64_t* digits, void* workspace,
+                            size_t workspace_bytes, void* state, size_t state_bytes, void* stream);
 
 #ifdef __cplusplus
 }
